@@ -19,9 +19,15 @@ edges to rank 0, LUT broadcast; everything else is rank-local (weak scaling).
       --master-port P bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline` (implicit-GEMM
-conv kernels, HIP-event timed inside the timed region), `predict_only` / `segment_only` (the two
-halves of the timed region), `cpu_baseline` (the repo's CPU restatement timed on this node's host
-cores; N=1 only) and `modes` (speed and max error of every precision mode on the same blocks).
+conv kernels, HIP-event timed inside the timed region) and `predict_only` / `segment_only` (the two
+halves of the timed region).  A plain run does nothing else: set-up, warm-up, the timed region, the
+line.  `--full` adds what takes runs of its own: `cpu_baseline` (the repo's CPU restatement timed on
+this node's host cores, and the parity checks against it; N=1 only), `modes` (speed and max error of
+every precision mode on the same blocks), `whole_volume`, the `drivers` and `train` legs, the
+single-lane roofline figures and the segmentation stage's repeat pass.
+
+`--dump-outputs DIR` writes what the timed run computed (the segmentation per threshold and the
+affinities it read) at fixed voxels of the box to DIR/*.npy, so that two builds can be compared.
 """
 import argparse
 import json
@@ -170,6 +176,28 @@ def cpu_baseline(raw_blocks, affs_u8_host, seg_blocks):
         "cores_note": "cores = threads used (torch intra-op threads of the predict restatement, pool threads of the segment one): the affinity mask, "
                       "capped by the cgroup CPU quota and by BSMI_BENCH_CORES (default 16 = one GPU's share of the node's host cores); cores_affinity = the uncapped mask",
     }, outs, frags, (E, Sc)
+
+
+DUMP_SAMPLE = 1 << 20   # voxels of the job's box that --dump-outputs writes (all ranks together): 38 MB
+
+
+def dump_outputs(out_dir, pipe, segs, rank, world):
+    """--dump-outputs: what the timed run handed its caller -- the segmentation of the box per threshold (int64 ids as float64,
+    exact below 2^53) and the uint8 affinities it was computed from (as float32) -- at DUMP_SAMPLE / world voxels of this rank's
+    slab, one in each of that many equal runs of the z-major order, at an offset drawn from a generator seeded with 0.
+    -> DIR/segmentation.npy (thresholds, voxels), DIR/affinities.npy (3, voxels); `_rank<r>` before .npy for N > 1."""
+    shape = pipe.seg.shape
+    n = int(np.prod(shape))
+    m = min(n, DUMP_SAMPLE // world)
+    stride = n // m
+    idx = np.arange(m, dtype=np.int64) * stride + np.random.default_rng(0).integers(0, stride, m)
+    zyx = tuple(torch.from_numpy(a.astype(np.int64)).to(pipe.seg.dev) for a in np.unravel_index(idx, shape))
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    affs = pipe.seg.interior(pipe.seg.affs)[(slice(None),) + zyx]
+    np.save(os.path.join(out_dir, f"affinities{suffix}.npy"), affs.float().cpu().numpy())
+    if segs is not None:
+        np.save(os.path.join(out_dir, f"segmentation{suffix}.npy"), segs[(slice(None),) + zyx].double().cpu().numpy())
 
 
 def same_partition(a, b):
@@ -538,14 +566,19 @@ def main():
                     help="start a block's segmentation as soon as the blocks it reads are predicted (default: stage by stage; +3 %% end to end, conv launches 8 %% slower)")
     ap.add_argument("--overlap-lanes", type=int, default=3, help="--overlap: lanes that take tasks while blocks are still being predicted")
     ap.add_argument("--no-segment", action="store_true", help="predict only (diagnostic; not the headline metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cpu_baseline and its parity checks, modes, whole_volume, the drivers and train legs, "
+                         "single-lane roofline, the segmentation stage's repeat pass (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region: its segmentation and affinities at fixed voxels of the box as DIR/*.npy (float64 / float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip `cpu_baseline`, its parity checks and `modes`")
     ap.add_argument("--pred-lanes", type=int, default=2,
                     help="engines whose forward passes overlap, block k on engine k mod K (measured on 64 blocks: 1 lane 96.4, 2 lanes 103.6, 3 lanes 96.7 Mvoxels/s)")
-    ap.add_argument("--no-modes", action="store_true", help="skip the per-precision predict lines (speed and error of f32 / bf16x3 / bf16)")
-    ap.add_argument("--no-train", action="store_true", help="skip the `train` leg (ms per training step in both arithmetics)")
-    ap.add_argument("--no-drivers", action="store_true", help="skip the `drivers` leg (bs predict + bs segment on an on-disk Zarr store of the whole volume)")
-    ap.add_argument("--drivers-box", action="store_true", help="`drivers` leg on the box of --steps blocks instead of the whole volume")
-    ap.add_argument("--no-whole-volume", action="store_true", help="skip the `whole_volume` leg (the whole 1024^3 volume, resident, over all ranks)")
+    ap.add_argument("--no-modes", action="store_true", help="--full: skip the per-precision predict lines (speed and error of f32 / bf16x3 / bf16)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the `train` leg (ms per training step in both arithmetics)")
+    ap.add_argument("--no-drivers", action="store_true", help="--full: skip the `drivers` leg (bs predict + bs segment on an on-disk Zarr store of the whole volume)")
+    ap.add_argument("--drivers-box", action="store_true", help="--full: `drivers` leg on the box of --steps blocks instead of the whole volume")
+    ap.add_argument("--no-whole-volume", action="store_true", help="--full: skip the `whole_volume` leg (the whole 1024^3 volume, resident, over all ranks)")
     ap.add_argument("--profile-every", type=int, default=4,
                     help="per-launch HIP-event timing (the roofline figures) on every Nth block of the timed region")
     ap.add_argument("--cpu-predict-blocks", type=int, default=2)
@@ -580,13 +613,13 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus}")
-    # The two side legs of the default one-GPU run -- the drivers on the whole volume as an on-disk store, the training step -- run
+    # The two side legs of the --full one-GPU run -- the drivers on the whole volume as an on-disk store, the training step -- run
     # FIRST, each in a process of its own, while this process has not touched the GPU yet: that is how a user runs those commands
     # (one process, the card to itself).  Measured in round 4: inside this process after its resident pipelines `bs segment` spent 1.3 s
     # allocating its slab (0.03 s alone) and the training step's second stream gained nothing (21.6 against 18.5 ms); in a child
     # beside this process's 23 idle hardware queues `bs segment` took 3.9 s instead of 2.0.
     side_legs = {}
-    if rank == 0 and world == 1 and not args.force_dist and not os.environ.get("BSMI_BENCH_LEGS_INPROC"):
+    if args.full and rank == 0 and world == 1 and not args.force_dist and not os.environ.get("BSMI_BENCH_LEGS_INPROC"):
         import shutil
         import subprocess
         tmp_root = os.environ.get("BSMI_BENCH_TMP") or __import__("tempfile").gettempdir()
@@ -684,6 +717,8 @@ def main():
     segs = pipe.run(vol)
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, segs, rank, world)
     totals, executed_flops = None, 0.0
     for m in engines:  # the profiled launches of every predict lane together
         t = m.profile_totals(reset=True)
@@ -692,7 +727,7 @@ def main():
         m.profile(False)
     t_pred, t_seg = pipe.t_predict, 0.0
     single_lane = None
-    if len(engines) > 1:
+    if args.full and len(engines) > 1:
         # the same launches with the card to themselves (outside the timed region): eight blocks on lane 0 alone, every launch timed
         from bootstrapper_amd.unet import extract_block_reflect
         in_block = tuple(o + 2 * c for o, c in zip(OUT_BLOCK, CONTEXT))
@@ -712,7 +747,7 @@ def main():
             single_lane = {"achieved": fl1 / (ms1 * 1e-3) / 1e12, "frac": fl1 / (ms1 * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS[args.precision],
                            "avg_launch_ms": ms1 / max(n1, 1), "launches": int(n1), "executed_mfma_frac": ex1 / (ms1 * 1e-3) / 1e12 / dense,
                            "what": "eight blocks on one lane alone after the timed region: the per-launch figures without another forward pass beside them"}
-    if not args.no_segment:
+    if args.full and not args.no_segment:
         # the segmentation half on its own (outside the timed region: there it overlaps the predict stream): the same
         # slab of affinities again, from fragments to the relabelled volumes; must reproduce the timed run's result
         first = segs.clone()
@@ -788,16 +823,18 @@ def main():
     if not args.no_segment:
         # two figures: the stage inside the timed region (what the pipeline pays, what the CPU ratio is taken from) and the
         # same stage repeated afterwards; they agree once the slab-sized torch paths have been used before the timed region
-        # (SlabSegmenter.prime).  With --overlap the stage is not separable and only the repeated pass is given.
+        # (SlabSegmenter.prime).  With --overlap the stage is not separable and only the repeated pass is given (--full).
         t_in = max(dt - t_pred, 1e-9) if not args.overlap else t_seg
-        seg_vox_s = nvox / t_in
-        out["segment_only"] = {"note": "seconds: end of the predict stage to the end of the timed region (fragments -> relabelled volumes); "
-                                       "repeat_pass: the same stage again on the same affinities after the timed region",
-                               "Mvoxels_per_s": seg_vox_s / 1e6, "seconds": t_in, "bytes_per_voxel": 38,
-                               "hbm_frac": 38.0 * seg_vox_s / world / HBM_PEAK_BYTES,
-                               "repeat_pass": {"seconds": t_seg, "Mvoxels_per_s": nvox / t_seg / 1e6},
-                               "fragments": int(len(pipe.seg.nodes)), "segments": [int(len(np.unique(c))) for c in pipe.seg.luts]}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if t_in > 0:
+            seg_vox_s = nvox / t_in
+            out["segment_only"] = {"note": "seconds: end of the predict stage to the end of the timed region (fragments -> relabelled volumes)"
+                                           + ("; repeat_pass: the same stage again on the same affinities after the timed region" if args.full else ""),
+                                   "Mvoxels_per_s": seg_vox_s / 1e6, "seconds": t_in, "bytes_per_voxel": 38,
+                                   "hbm_frac": 38.0 * seg_vox_s / world / HBM_PEAK_BYTES,
+                                   "fragments": int(len(pipe.seg.nodes)), "segments": [int(len(np.unique(c))) for c in pipe.seg.luts]}
+            if args.full:
+                out["segment_only"]["repeat_pass"] = {"seconds": t_seg, "Mvoxels_per_s": nvox / t_seg / 1e6}
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         nb = max(1, min(args.cpu_predict_blocks, args.steps))
         raws = [extract_block_reflect(vol, [o + lo - c for o, lo, c in zip(pipe.origin, b, CONTEXT)], in_block)
                 for b, _ in pipe.seg.boxes[:nb]]
@@ -859,7 +896,7 @@ def main():
         out["per_rank"] = [per_rank]
     pipe_origin = pipe.origin
     edge = args.volume // OUT_BLOCK[0]
-    if not args.no_segment and not args.no_whole_volume and edge % world == 0 and (args.steps, job) != (edge ** 3 // world, (edge // world, edge, edge)):
+    if args.full and not args.no_segment and not args.no_whole_volume and edge % world == 0 and (args.steps, job) != (edge ** 3 // world, (edge // world, edge, edge)):
         del pipe, segs
         pipe = segs = None
         torch.cuda.empty_cache()
@@ -871,7 +908,7 @@ def main():
             if world > 1:
                 raise
             out["whole_volume"] = {"error": f"{type(exc).__name__}: {exc}"}
-    elif not args.no_segment and not args.no_whole_volume and edge % world == 0:
+    elif args.full and not args.no_segment and not args.no_whole_volume and edge % world == 0:
         out["whole_volume"] = {"what": "the timed region above IS the whole volume", "Mvoxels_per_s": value, "seconds": dt}
     if "drivers" in side_legs:
         out["drivers"] = side_legs["drivers"]
@@ -880,7 +917,7 @@ def main():
         resident = out.get("whole_volume", {}).get("Mvoxels_per_s")
         out["drivers"]["resident_Mvoxels_per_s"] = resident
         out["drivers"]["frac_of_resident"] = out["drivers"]["Mvoxels_per_s"] / resident if resident else None
-    elif rank == 0 and world == 1 and not args.no_drivers and not args.no_segment:
+    elif args.full and rank == 0 and world == 1 and not args.no_drivers and not args.no_segment:
         # in this process: the box of `--steps` blocks when the volume's datasets would not fit the temporary directory (or
         # BSMI_BENCH_LEGS_INPROC / --force-dist)
         import shutil
@@ -904,7 +941,7 @@ def main():
         out["drivers"]["frac_of_resident"] = out["drivers"]["Mvoxels_per_s"] / resident if resident else None
     if "train" in side_legs:
         out["train"] = side_legs["train"]
-    elif rank == 0 and world == 1 and not args.no_train:
+    elif args.full and rank == 0 and world == 1 and not args.no_train:
         pipe = segs = vol = None
         torch.cuda.empty_cache()
         try:

@@ -55,3 +55,31 @@ def test_regrid_ids_and_edge_check():
     a = rng.integers(0, 5, (128, 128, 128)).astype(np.uint64)
     perm = np.array([0, 9, 7, 5, 3], np.uint64)
     assert B.same_partition(a, perm[a]) and not B.same_partition(a, np.where(a == 4, np.uint64(3), a))
+
+
+def test_dump_outputs_writes_fixed_voxels(tmp_path):
+    """--dump-outputs: the segmentation and the affinities of the timed run at the same voxels every run (one in each equal run
+    of the z-major order), in float64 / float32 without loss, within 64 MB at the benchmark's sample size"""
+    import types
+    import torch
+    B = _bench()
+    assert B.DUMP_SAMPLE * (3 * 8 + 3 * 4) <= 64 * 2 ** 20
+    B.DUMP_SAMPLE = 4096
+    shape, ctx = (16, 32, 64), (4, 4, 4)
+    g = torch.Generator().manual_seed(0)
+    affs = torch.randint(0, 256, (3,) + tuple(s + 2 * c for s, c in zip(shape, ctx)), dtype=torch.uint8, generator=g)
+    segs = torch.randint(1, 2 ** 40, (3,) + shape, dtype=torch.int64, generator=g)
+    interior = lambda t: t[(Ellipsis,) + tuple(slice(c, c + s) for c, s in zip(ctx, shape))]  # noqa: E731
+    pipe = types.SimpleNamespace(seg=types.SimpleNamespace(shape=shape, dev=torch.device("cpu"), affs=affs, interior=interior))
+    for run in ("a", "b"):
+        B.dump_outputs(str(tmp_path / run), pipe, segs, 0, 1)
+    a, s = np.load(tmp_path / "a" / "affinities.npy"), np.load(tmp_path / "a" / "segmentation.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 4096) and s.dtype == np.float64 and s.shape == (3, 4096)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "affinities.npy")) and np.array_equal(s, np.load(tmp_path / "b" / "segmentation.npy"))
+    flat_s, flat_a = segs.reshape(3, -1).numpy(), interior(affs).reshape(3, -1).numpy()
+    hit = flat_s[0].reshape(4096, -1) == s[0][:, None]          # the ids are distinct: where each sampled one sits in its run
+    assert (hit.sum(1) == 1).all()
+    at = np.arange(4096) * hit.shape[1] + hit.argmax(1)
+    assert np.array_equal(flat_s[:, at], s) and np.array_equal(flat_a[:, at], a)
+    B.dump_outputs(str(tmp_path / "r"), pipe, None, 1, 2)        # predict only, rank 1 of 2: its share of the sample
+    assert sorted(os.listdir(tmp_path / "r")) == ["affinities_rank1.npy"] and np.load(tmp_path / "r" / "affinities_rank1.npy").shape == (3, 2048)

@@ -7,53 +7,71 @@
 // file floods, the device continues -- also in the block pipeline, whose 16 lanes made the device loop 0.8 s per block.
 // bsmi_seg_set_host_flood(h, 0) selects the device loop (asynchronous; kept and tested).
 //
-// Algorithm: exactly ws3_flood_kernel's (and oracle/seg_ref.c's) -- entries (MAXD2 - d2) << 46 | age << 23 | voxel, ordered by
-// (value, age) only; seeds pushed in raster order with age 0; heappush sifts up while strictly smaller than the parent,
-// heappop moves the last entry to the root and sifts it down towards the smaller child; neighbours in the order
-// [-HW, -W, -1, +1, +W, +HW], each unlabelled masked neighbour labelled and pushed with the next age.
+// Algorithm: exactly ws3_flood_kernel's (and oracle/seg_ref.c's) -- entries ordered by (MAXD2 - d2, age) only; seeds pushed
+// in raster order with age 0; heappush sifts up while strictly smaller than the parent, heappop moves the last entry to the
+// root and sifts it down towards the smaller child; neighbours in the order [-HW, -W, -1, +1, +W, +HW], each unlabelled
+// masked neighbour labelled and pushed with the next age.
 #include <cstddef>
 #include <cstdint>
 #include <vector>
 
 namespace bsmi {
 
-void host_flood3(int D, int H, int W, const uint8_t* mask, const int32_t* d2, int32_t* lab) {
+// Entry: NARROW -- one 64-bit word (MAXD2 - d2) << 46 | age << 23 | voxel (what ws3_flood_kernel packs; volumes below 2^23
+// voxels with D^2 + H^2 + W^2 + 2 D + 1 < 2^18), ordered by the bits above the voxel; otherwise WIDE -- the key
+// (MAXD2 - d2) << 37 | age (d2 < 3 * 4096^2 + 2 * 4096 + 1 < 2^26, age < the voxel count <= 2^36) and the voxel beside it.
+// Same order either way: (value, age), the voxel never compared.
+struct FloodEntryNarrow {
+  uint64_t e;
+  static constexpr uint64_t MAXD2 = (1u << 18) - 1;
+  FloodEntryNarrow(uint64_t d2, uint64_t age, size_t q) : e(((MAXD2 - d2) << 46) | (age << 23) | (uint64_t)q) {}
+  bool operator<(const FloodEntryNarrow& o) const { return (e >> 23) < (o.e >> 23); }
+  size_t voxel() const { return (size_t)(e & 0x7fffffu); }
+};
+struct FloodEntryWide {
+  uint64_t key, q;
+  static constexpr uint64_t MAXD2 = (1u << 26) - 1;
+  FloodEntryWide(uint64_t d2, uint64_t age, size_t q_) : key(((MAXD2 - d2) << 37) | age), q((uint64_t)q_) {}
+  bool operator<(const FloodEntryWide& o) const { return key < o.key; }
+  size_t voxel() const { return (size_t)q; }
+};
+
+template <typename E>
+static void flood3(int D, int H, int W, const uint8_t* mask, const int32_t* d2, int32_t* lab) {
   const size_t n = (size_t)D * H * W, hw = (size_t)H * W;
-  constexpr uint64_t MAXD2 = (1u << 18) - 1;
-  std::vector<uint64_t> heap;
+  std::vector<E> heap;
   heap.reserve(n / 4 + 1024);
-  auto smaller = [](uint64_t a, uint64_t b) { return (a >> 23) < (b >> 23); };
-  auto push = [&](uint64_t it) {
+  auto push = [&](const E it) {
     size_t c = heap.size();
     heap.push_back(it);
     while (c > 0) {
       const size_t p = (c + 1) / 2 - 1;
-      const uint64_t pv = heap[p];
-      if (smaller(it, pv)) { heap[c] = pv; c = p; } else break;
+      const E pv = heap[p];
+      if (it < pv) { heap[c] = pv; c = p; } else break;
     }
     heap[c] = it;
   };
   for (size_t j = 0; j < n; ++j)
-    if (lab[j] != 0) push(((MAXD2 - (uint64_t)d2[j]) << 46) | (uint64_t)j);
+    if (lab[j] != 0) push(E((uint64_t)d2[j], 0, j));
   uint64_t age = 0;
   while (!heap.empty()) {
-    const uint64_t e = heap[0];
+    const E e = heap[0];
     const size_t items = heap.size() - 1;
-    const size_t idx = (size_t)(e & 0x7fffffu);
+    const size_t idx = e.voxel();
     const int32_t l = lab[idx];
     if (items > 0) {
-      const uint64_t last = heap[items];
+      const E last = heap[items];
       size_t i = 0;
       for (;;) {
         const size_t c1 = 2 * i + 1, c2 = c1 + 1;
         if (c1 >= items) break;
         size_t sm = i;
-        uint64_t smv = last;
-        const uint64_t v1 = heap[c1];
-        if (smaller(v1, smv)) { sm = c1; smv = v1; }
+        E smv = last;
+        const E v1 = heap[c1];
+        if (v1 < smv) { sm = c1; smv = v1; }
         if (c2 < items) {
-          const uint64_t v2 = heap[c2];
-          if (smaller(v2, smv)) { sm = c2; smv = v2; }
+          const E v2 = heap[c2];
+          if (v2 < smv) { sm = c2; smv = v2; }
         }
         if (sm == i) break;
         heap[i] = smv;
@@ -71,9 +89,17 @@ void host_flood3(int D, int H, int W, const uint8_t* mask, const int32_t* d2, in
       if (!mask[q] || lab[q] != 0) continue;
       ++age;
       lab[q] = l;
-      push(((MAXD2 - (uint64_t)d2[q]) << 46) | (age << 23) | (uint64_t)q);
+      push(E((uint64_t)d2[q], age, q));
     }
   }
+}
+
+void host_flood3(int D, int H, int W, const uint8_t* mask, const int32_t* d2, int32_t* lab) {
+  const size_t n = (size_t)D * H * W;
+  if (n < ((size_t)1 << 23) && (size_t)D * D + (size_t)H * H + (size_t)W * W + 2 * D + 1 < ((size_t)1 << 18))
+    flood3<FloodEntryNarrow>(D, H, W, mask, d2, lab);
+  else
+    flood3<FloodEntryWide>(D, H, W, mask, d2, lab);
 }
 
 }  // namespace bsmi

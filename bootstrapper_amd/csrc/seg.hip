@@ -211,6 +211,29 @@ __global__ __launch_bounds__(WS_T) void ws_seeds_kernel(const uint8_t* __restric
     }
     __syncthreads();
     // b2. per voxel: min over y' of g(y',x)^2 + (y-y')^2   (exact, integers)
+    if (n >= (1 << 20)) {
+      // full-size sections: outwards from the own row, as the LDS path does -- a row k away cannot improve on a best <= k^2,
+      // so a voxel walks O(distance) rows instead of H (the same minimum; a 1250^2 slice with one straight edge, distances up
+      // to 625: the kernel 645 -> 108 ms)
+      for (int i = tid; i < n; i += WS_T) {
+        const int y = i / W;
+        const int g0 = g[i];
+        int best = g0 < INF ? g0 * g0 : INF;
+        for (int k = 1; k < H && k * k < best; ++k) {
+          if (y - k >= 0) {
+            const int gg = g[i - k * W];
+            const int v = gg < INF ? gg * gg + k * k : INF;
+            best = v < best ? v : best;
+          }
+          if (y + k < H) {
+            const int gg = g[i + k * W];
+            const int v = gg < INF ? gg * gg + k * k : INF;
+            best = v < best ? v : best;
+          }
+        }
+        d2[i] = best;
+      }
+    } else
     for (int i = tid; i < n; i += WS_T) {
       const int y = i / W, x = i - y * W;
       int best = INF;
@@ -603,6 +626,237 @@ __global__ __launch_bounds__(64 * FLOOD_WAVES) void ws_flood_kernel(int D, int H
     out[i] = l ? (uint64_t)l + off : 0ull;
   }
   (void)status;
+}
+
+// The flood of slices of 2^20 voxels and more (up to 4096 x 4096): ws_flood_kernel's packed entry has 20 bits for the age and
+// the voxel.  Here an entry is a 64-bit key (MAXD2 - d2) << 32 | age -- the whole order, below 2^63, so that flood_smaller's
+// trick (the sign of the difference) stays exact -- and a 32-bit voxel index beside it, in parallel arrays.  Same algorithm
+// as ws_flood_kernel<false> and oracle/seg_ref.c:flood, bit for bit.
+//
+// One slice per workgroup (one wave): big slices come a few to a call, so a wave has a whole CU's LDS for the top
+// FLOOD_WIDE_LDS_LEVELS levels of its heap (8191 entries, 96 KiB); deeper levels spill to HBM (`spill_key` / `spill_idx`,
+// `spill_stride` entries per slice).  A blobby 1250^2 slice queues ~10^5 entries, so a sift-down usually ends 2-5 levels
+// under the LDS part.  One round trip per spilled level would make it the loop's cost; instead, when the walk reaches the
+// bottom LDS level, lanes 0-61 fetch the 62 entries of the next five levels under the current node in one round of loads
+// (2 + 4 + 8 + 16 + 32), and the walk goes on through them with v_readlane.  Windows are rooted at depths 12, 17, 22, so
+// every spilled node belongs to exactly one window, at one place in it: it has an owner lane, and ALL its global loads and
+// stores -- window fetches, sift-down moves, sift-up reads and moves -- are issued by that lane alone.  A lane's accesses to
+// an address follow its own program order, so no fence is needed between a store and a later window's load.
+constexpr int FLOOD_WIDE_LDS_LEVELS = 13;
+constexpr int FLOOD_WIDE_LDS_HEAP = (1 << FLOOD_WIDE_LDS_LEVELS) - 1;
+
+// owner lane of spilled heap node i (i >= FLOOD_WIDE_LDS_HEAP): its depth below the window root k = 1..5 and position j in
+// that level of the window -> lane 2^k - 2 + j
+__device__ __forceinline__ int flood_wide_owner(uint32_t i) {
+  const int d = 31 - __builtin_clz(i + 1);
+  const int k = (d - FLOOD_WIDE_LDS_LEVELS) % 5 + 1;
+  return (1 << k) - 2 + (int)((i + 1) & ((1u << k) - 1));
+}
+
+#ifdef BSMI_FLOOD_STATS  // dev build: where the wide flood's pops go, summed over slices (tools/probe_large_sections.py --stats)
+// [0] pops  [1] sift-down moves within LDS  [2] window fetches  [3] sift-down moves within spilled levels  [4] pushes
+// [5] sift-up moves  [6] sift-up parent reads from spilled levels  [7] `last` entries read from spilled levels
+// [8] largest heap (max over slices)  [9] 100 MHz ticks of the pop loop  [10] slices
+__device__ unsigned long long g_flood_stats[16];
+extern "C" int bsmi_debug_flood_stats(unsigned long long* out, int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_flood_stats), sizeof(unsigned long long) * 16) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long zero[16] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_flood_stats), zero, sizeof zero) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#define FW_STAT(i, v) (st[i] += (v))
+#else
+#define FW_STAT(i, v) ((void)0)
+#endif
+
+__global__ __launch_bounds__(64) void ws_flood_wide_kernel(int D, int H, int W, WsScratch s, uint64_t* spill_key, uint32_t* spill_idx,
+                                                           size_t spill_stride, uint64_t* __restrict__ frags) {
+  constexpr int LH = FLOOD_WIDE_LDS_HEAP;
+  __shared__ uint64_t hk[LH];
+  __shared__ uint32_t hx[LH];
+  const int lane = threadIdx.x;
+  const int z = blockIdx.x;
+  if (z >= D) return;
+  const int n = H * W;
+  const uint8_t* mask = s.mask + (size_t)z * n;
+  const int32_t* d2 = s.d2 + (size_t)z * n;
+  int32_t* lab = s.lab + (size_t)z * n;
+  uint64_t* gk = spill_key + (size_t)z * spill_stride;  // gk[i - LH], gx[i - LH]: spilled node i (i >= LH)
+  uint32_t* gx = spill_idx + (size_t)z * spill_stride;
+  // the whole wave walks the one loop in lockstep, as in ws_flood_kernel: every value out of memory goes through
+  // v_readfirstlane / v_readlane, so that the loop's control lives on the scalar unit
+  {
+    constexpr uint64_t MAXD2 = 0x7fffffffull;  // d2 <= 4096^2 + 4095^2 < 2^25 here (H, W <= 4096: launcher): keys < 2^63
+    auto uni = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
+    auto rl64 = [](uint64_t v, int l) -> uint64_t {
+      const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, l), hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l);
+      return ((uint64_t)hi << 32) | lo;
+    };
+    auto smaller = [](uint64_t a_, uint64_t b_) -> bool { return (int64_t)(a_ - b_) < 0; };
+    int items = 0;
+#ifdef BSMI_FLOOD_STATS
+    uint64_t st[11] = {};
+    bool popping = false;
+    uint64_t t0 = 0;
+#endif
+    // node i (LDS or spilled) -> wave-uniform key and index.  LDS writes are issued by every active lane (same address, same value).
+    struct Ent { uint64_t k; uint32_t x; };
+    auto hget = [gk, gx, lane, rl64](int i) -> Ent {
+      if (i < LH) return {hk[i], hx[i]};
+      const int o = flood_wide_owner((uint32_t)i);
+      uint64_t kv = 0;
+      uint32_t xv = 0;
+      if (lane == o) { kv = gk[i - LH]; xv = gx[i - LH]; }
+      return {rl64(kv, o), (uint32_t)__builtin_amdgcn_readlane((int)xv, o)};
+    };
+    auto hset = [gk, gx, lane](int i, uint64_t k_, uint32_t x_) {
+      if (i < LH) { hk[i] = k_; hx[i] = x_; return; }
+      if (lane == flood_wide_owner((uint32_t)i)) { gk[i - LH] = k_; gx[i - LH] = x_; }
+    };
+    auto push = [&](uint64_t ik, uint32_t ix) {
+      int c = uni(items++);
+#ifdef BSMI_FLOOD_STATS
+      if (popping) FW_STAT(4, 1);
+      if ((uint64_t)items > st[8]) st[8] = items;
+#endif
+      while (c > 0) {
+        const int p = (c - 1) >> 1;
+        const Ent pe = hget(p);
+#ifdef BSMI_FLOOD_STATS
+        if (popping && p >= LH) FW_STAT(6, 1);
+#endif
+        if (!smaller(ik, pe.k)) break;
+        hset(c, pe.k, pe.x);
+#ifdef BSMI_FLOOD_STATS
+        if (popping) FW_STAT(5, 1);
+#endif
+        c = p;
+      }
+      hset(c, ik, ix);
+    };
+    // seeds in raster order, age 0
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      const int i = i0 + lane;
+      const int li = i < n ? lab[i] : 0;
+      unsigned long long seeds = __ballot(li != 0);
+      while (seeds) {
+        const int k = __ffsll(seeds) - 1;
+        seeds &= seeds - 1;
+        const int j = i0 + k;
+        push((MAXD2 - (uint64_t)(uint32_t)uni(d2[j])) << 32, (uint32_t)j);
+      }
+    }
+    uint32_t age = 0;
+    const int k4 = lane & 3;  // lanes 4-63 repeat lanes 0-3's neighbour fetches (same addresses: no extra lines)
+    const int dq = k4 == 0 ? -W : (k4 == 1 ? -1 : (k4 == 2 ? 1 : W));
+    // y = idx / W by a multiply: m = ceil(2^36 / W) = (2^36 + e) / W with 0 <= e < W, so idx * m / 2^36 = idx / W + idx * e / (W 2^36),
+    // and the error term is < 1 / W -- it cannot carry past the next integer -- whenever idx * e < 2^36, which holds for
+    // idx < 2^24 (the handle's H * W <= 4096^2) and W <= 4096 (the launcher refuses wider rows).  (The 32-bit reciprocal of
+    // ws_flood_kernel is exact only for idx < 2^20.)
+    const uint64_t mW = (((uint64_t)1 << 36) + (uint64_t)W - 1) / (uint64_t)W;
+    // window of a sift-down: lane l < 62 holds the node at depth k = log2(l + 2) under the window root, position l + 2 - 2^k
+    const int wl_k = 31 - __builtin_clz((uint32_t)lane + 2);
+    const int wl_j = lane + 2 - (1 << wl_k);
+#ifdef BSMI_FLOOD_STATS
+    popping = true;
+    t0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    while (items > 0) {
+      FW_STAT(0, 1);
+      const uint64_t ek = hk[0];
+      const uint32_t ex = hx[0];
+      (void)ek;
+      items = uni(items - 1);
+      const int idx = uni((int)ex);
+      const int y = (int)(((uint64_t)(uint32_t)idx * mW) >> 36), x = idx - y * W;
+      // neighbour order [-W, -1, +1, +W]: lane k looks at neighbour k & 3
+      const bool okk = k4 == 0 ? y > 0 : (k4 == 1 ? x > 0 : (k4 == 2 ? x < W - 1 : y < H - 1));
+      const int qk = okk ? idx + dq : idx;
+      const int lme = lab[idx], mk = mask[qk], lk = lab[qk], dk = d2[qk];
+      if (items > 0) {
+        // sift the last element down from the root (skimage heappop order): the smaller child, the left one on a tie
+        const Ent le = hget(items);
+        FW_STAT(7, items >= LH ? 1 : 0);
+        const uint64_t lastk = le.k;
+        const uint32_t lastx = le.x;
+        int i = 0;
+        bool placed = false;
+        while (true) {  // LDS levels
+          const int c1 = 2 * i + 1, c2 = c1 + 1;
+          if (c1 >= items) { placed = true; break; }
+          if (c1 >= LH) break;  // i is on the bottom LDS level: the children are spilled
+          const uint64_t v1 = hk[c1], v2 = hk[c2];  // (c2 < LH; entry c2 = items is read and not looked at)
+          int sm = i;
+          uint64_t smv = lastk;
+          if (smaller(v1, smv)) { sm = c1; smv = v1; }
+          if (c2 < items && smaller(v2, smv)) { sm = c2; smv = v2; }
+          if (sm == i) { placed = true; break; }
+          hk[i] = smv;
+          hx[i] = hx[sm];
+          FW_STAT(1, 1);
+          i = sm;
+        }
+        while (!placed) {  // spilled levels, five at a time
+          uint64_t wk = 0;
+          uint32_t wx = 0;
+          {
+            const uint32_t q = ((uint32_t)(i + 1) << wl_k) - 1 + (uint32_t)wl_j;  // < 2^30: i < 2^24, wl_k <= 5
+            if (lane < 62 && q < (uint32_t)items) { wk = gk[q - LH]; wx = gx[q - LH]; }
+          }
+          FW_STAT(2, 1);
+          int wj = 0;  // position of i in its level of the window (the root: level 0, position 0)
+          int kk = 0;
+          for (; kk < 5; ++kk) {
+            const int c1 = 2 * i + 1, c2 = c1 + 1;
+            if (c1 >= items) { placed = true; break; }
+            const int l1 = (2 << kk) - 2 + 2 * wj;  // lane of c1 (c2: l1 + 1)
+            const uint64_t v1 = rl64(wk, l1), v2 = rl64(wk, l1 + 1);
+            int sm = i, sl = 0;
+            uint64_t smv = lastk;
+            if (smaller(v1, smv)) { sm = c1; smv = v1; sl = l1; }
+            if (c2 < items && smaller(v2, smv)) { sm = c2; smv = v2; sl = l1 + 1; }
+            if (sm == i) { placed = true; break; }
+            hset(i, smv, (uint32_t)__builtin_amdgcn_readlane((int)wx, sl));
+            FW_STAT(3, 1);
+            wj = 2 * wj + (sm == c2 ? 1 : 0);
+            i = uni(sm);
+          }
+        }
+        hset(i, lastk, lastx);
+      }
+      const int l = uni(lme);
+      const bool cand = okk && mk && lk == 0;
+      // the neighbours to take, in the order [-W, -1, +1, +W]
+      for (uint32_t m = (uint32_t)__ballot(cand) & 0xfu; m; m &= m - 1) {
+        const int k = __ffs((int)m) - 1;
+        const int q = __builtin_amdgcn_readlane(qk, k);
+        const uint64_t dd = (uint64_t)(uint32_t)__builtin_amdgcn_readlane(dk, k);
+        ++age;
+        lab[q] = l;
+        push(((MAXD2 - dd) << 32) | age, (uint32_t)q);
+      }
+    }
+#ifdef BSMI_FLOOD_STATS
+    st[9] = __builtin_amdgcn_s_memrealtime() - t0;
+    st[10] = 1;
+    if (lane == 0) {
+      for (int k = 0; k < 11; ++k)
+        if (k == 8) atomicMax(&g_flood_stats[k], (unsigned long long)st[k]);
+        else atomicAdd(&g_flood_stats[k], (unsigned long long)st[k]);
+    }
+#endif
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  const uint64_t off = s.offs[z];
+  uint64_t* out = frags + (size_t)z * n;
+  for (int i = lane; i < n; i += 64) {
+    const int l = lab[i];
+    out[i] = l ? (uint64_t)l + off : 0ull;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2314,6 +2568,7 @@ struct bsmi_seg {
   WsScratch ws{};
   uint64_t* flood_spill = nullptr;
   size_t flood_spill_stride = 0;
+  uint32_t* flood_spill_idx = nullptr;  // [max_vox] voxel indices of ws_flood_wide_kernel's spilled entries (slices of 2^20 voxels and more only)
   AggWs agg{};
   FragWs frag{};
   uint64_t* crop_tmp = nullptr;  // [max_vox] cropped fragments before relabelling
@@ -2352,8 +2607,6 @@ int bsmi_seg_create(int device, const int64_t max_shape[3], bsmi_seg** out) {
   if (!max_shape || !out) BSMI_FAIL(BSMI_ERR_INVALID, "null argument");
   for (int d = 0; d < 3; ++d)
     if (max_shape[d] < 1 || max_shape[d] > 4096) BSMI_FAIL(BSMI_ERR_INVALID, "bad max_shape");
-  if (max_shape[1] * max_shape[2] >= (1 << 20))
-    BSMI_FAIL(BSMI_ERR_INVALID, "slices larger than 2^20 voxels are not supported by the flood kernel");
   BSMI_HIP(hipSetDevice(device));
   bsmi_seg* h = new bsmi_seg;
   h->device = device;
@@ -2368,6 +2621,7 @@ int bsmi_seg_create(int device, const int64_t max_shape[3], bsmi_seg** out) {
   h->ws.seedlab = nullptr;
   h->flood_spill_stride = ns;
   A(h->flood_spill, nv);
+  if (ns >= ((size_t)1 << 20)) A(h->flood_spill_idx, nv);  // (the wide flood's keys spill into flood_spill)
   AggWs& g = h->agg;
   static std::atomic<int> next_xcd{0};
   g.xcd_hint = next_xcd.fetch_add(1) & 7;
@@ -2460,7 +2714,8 @@ int bsmi_ws_fragments_seeds_u8(bsmi_seg* h, const uint8_t* affs_dev, const int64
   const int D = (int)shape[0], H = (int)shape[1], W = (int)shape[2];
   if (!fragments_in_xy) {
     const size_t n = (size_t)D * H * W;
-    if (n >= ((size_t)1 << 23) || (size_t)D * D + (size_t)H * H + (size_t)W * W + 2 * D + 1 >= ((size_t)1 << 18))
+    // the device flood's packed queue entry (ws3_flood_kernel); the host flood widens its entry where needed (flood_host.cpp)
+    if (!h->host_flood3 && (n >= ((size_t)1 << 23) || (size_t)D * D + (size_t)H * H + (size_t)W * W + 2 * D + 1 >= ((size_t)1 << 18)))
       BSMI_FAIL(BSMI_ERR_INVALID, "3-D watershed: volumes of 2^23 voxels or more are not supported by the flood's queue entries");
     WsScratch& w = h->ws;
     FragWs& f = h->frag;
@@ -2504,6 +2759,12 @@ int bsmi_ws_fragments_seeds_u8(bsmi_seg* h, const uint8_t* affs_dev, const int64
     BSMI_HIP(hipGetLastError());
     return BSMI_OK;
   }
+  // Slices of 2^20 voxels and more take ws_flood_wide_kernel, whose row index is exact for W <= 4096 and whose keys hold
+  // d2 < 2^25, i.e. H, W <= 4096.  check_seg_shape bounds a call's slice by the handle's H * W only, so a call may lay that
+  // area out as a longer row (e.g. 2796 x 6000 on a 4096 x 4096 handle): refused here, before anything runs.  (Such calls
+  // were refused before the wide flood existed: no handle took slices this large.)
+  if ((size_t)H * W >= ((size_t)1 << 20) && (H > 4096 || W > 4096))
+    BSMI_FAIL(BSMI_ERR_INVALID, "slices of 2^20 voxels or more must have H, W <= 4096 (got %d x %d)", H, W);
   WsScratch wsx = h->ws;
   bool compact = false;  // the flood's per-voxel state as one 32-bit record (set with the seeds kernel's LDS path below)
   wsx.seedlab = nullptr;
@@ -2541,7 +2802,12 @@ int bsmi_ws_fragments_seeds_u8(bsmi_seg* h, const uint8_t* affs_dev, const int64
   if (seeds_dev)
     hipLaunchKernelGGL(ws_seeds_out_kernel, dim3((unsigned)std::min<size_t>(((size_t)D * H * W + 255) / 256, 4096)), dim3(256), 0, s, D,
                        (size_t)H * W, wsx, seeds_dev);
-  if (compact)
+  if ((size_t)H * W >= ((size_t)1 << 20)) {
+    // beyond the packed entry's 20-bit voxel and age fields: one slice per workgroup, the heap's top levels in LDS
+    if (!h->flood_spill_idx) BSMI_FAIL(BSMI_ERR_STATE, "wide flood without its spill");
+    hipLaunchKernelGGL(ws_flood_wide_kernel, dim3(D), dim3(64), 0, s, D, H, W, h->ws, h->flood_spill, h->flood_spill_idx,
+                       h->flood_spill_stride, frags_dev);
+  } else if (compact)
     hipLaunchKernelGGL(ws_flood_kernel<true>, dim3((D + FLOOD_WAVES - 1) / FLOOD_WAVES), dim3(64 * FLOOD_WAVES), 0, s, D, H, W, h->ws, h->flood_spill,
                        h->flood_spill_stride, frags_dev, h->status_dev);
   else

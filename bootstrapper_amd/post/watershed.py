@@ -41,7 +41,7 @@ def simple_watershed(config, device=0):
     from .waterz import MERGE_FUNCTIONS
     if merge_function not in MERGE_FUNCTIONS:   # the reference's table (post/watershed.py:230-243) raises KeyError here
         raise KeyError(merge_function)
-    if affs.dtype != np.uint8:
+    if affs.dtype != np.uint8 and not np.issubdtype(affs.dtype, np.floating):
         raise NotImplementedError("the device path takes uint8 affinities (what `bs predict` stores)")
 
     if config.get("roi_offset") is not None:
@@ -54,6 +54,13 @@ def simple_watershed(config, device=0):
         data = np.concatenate([np.zeros_like(data[:1]), data])
     dev = torch.device("cuda", device)
     a = torch.from_numpy(np.ascontiguousarray(data)).to(dev)
+    if a.dtype != torch.uint8:   # float datasets holding exactly u8 / 255 (the values `bs predict` stores) go back to uint8
+        from .ws import as_u8_affinities
+        try:
+            a = as_u8_affinities(a, 1.0, device=device)
+        except ValueError:
+            raise NotImplementedError("float affinities must be exactly uint8 / 255: the device agglomeration scores uint8 "
+                                      "affinities") from None
     if config.get("mask_dataset"):
         mask = open_ds(config["mask_dataset"])
         m = torch.from_numpy((mask[mask.roi_to_slices(*roi)] > 0).astype(np.uint8)).to(dev)

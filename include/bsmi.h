@@ -244,7 +244,13 @@ int bsmi_extract_block_reflect_u8(const uint8_t *vol_dev, const int64_t vol_shap
  * watershed_from_affinities, :8-35 watershed_from_boundary_distance).
  * affs_dev: uint8 [3][D][H][W] (z,y,x nearest-neighbour affinities).
  * frags_dev: uint64 [D][H][W].  max_id_dev: uint64[1] (ws.py return value n+id_offset).
- * Only fragments_in_xy != 0 and max_affinity_value = 255 are implemented.        */
+ * Only fragments_in_xy != 0 and max_affinity_value = 255 are implemented.
+ * bsmi_seg_create limits: 1 <= max_shape[d] <= 4096 on every axis (so sections up to 4096 x 4096: slices of 2^20 voxels and
+ * more take the wide flood, whose spill the handle then allocates); fragment ids below 2^27.  The 3-D mode
+ * (fragments_in_xy = 0) with the device flood (bsmi_seg_set_host_flood(h, 0)) takes volumes below 2^23 voxels with
+ * D^2 + H^2 + W^2 + 2 D + 1 < 2^18; with the host flood (the default) volumes below 2^31 voxels (the device stages before
+ * it index voxels in 32 bits).  A call's slice is bounded by the handle's H * W; a slice of 2^20 voxels or more must also
+ * keep H, W <= 4096 (BSMI_ERR_INVALID otherwise).                                                                    */
 typedef struct bsmi_seg bsmi_seg;
 int bsmi_seg_create(int device, const int64_t max_shape[3], bsmi_seg **out);
 int bsmi_seg_destroy(bsmi_seg *h);

@@ -134,6 +134,13 @@ def _load():
         "bsmi_debug_check_guards": (i32, []),
         "bsmi_stream_create_cu_mask": (i32, [C.c_int, vp, C.c_int, C.POINTER(C.c_void_p)]),
         "bsmi_stream_destroy": (i32, [C.c_int, vp]),
+        "bsmi_eval_create": (i32, [i32, C.c_uint64, C.POINTER(p)]),
+        "bsmi_eval_destroy": (i32, [p]),
+        "bsmi_eval_aff_errors_u8": (i32, [p, vp, i64p, i64p, vp, i32, i64p, vp, C.POINTER(C.c_int32), i64p, C.c_float, C.c_float,
+                                          C.c_int64, vp, vp, vp, vp]),
+        "bsmi_eval_pairs_u64": (i32, [p, vp, vp, vp, i64p, i32, vp]),
+        "bsmi_eval_pairs_read": (i32, [p, vp, vp, vp, C.c_uint64, vp, vp]),
+        "bsmi_eval_status": (i32, [p, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -1,7 +1,8 @@
-"""`bs`-compatible command line for the hot path: `train`, `predict` and `segment` with the reference's
-flags (/root/reference/bootstrapper/cli.py:51-92, predict.py:243-266, segment.py:166-241).
+"""`bs`-compatible command line for the hot path: `train`, `predict`, `segment`, `refine` and `evaluate` with the reference's
+flags (/root/reference/bootstrapper/cli.py:51-92, predict.py:243-266, segment.py:166-241, evaluate.py:130-159).
     python -m bootstrapper_amd.cli predict 02_pred.toml -s 01 -ng 8
     python -m bootstrapper_amd.cli segment 03_seg.toml -ws -p 'thresholds=[0.2,0.5]'
+    python -m bootstrapper_amd.cli eval 04_eval_volume.toml
 """
 import click
 
@@ -71,10 +72,15 @@ from .refine import refine as _refine  # noqa: E402
 
 cli.add_command(_refine, "refine")
 
+from .evaluate import evaluate as _evaluate  # noqa: E402
+
+cli.add_command(_evaluate, "evaluate")
+
 # aliases of the reference CLI (cli.py:38-44)
 cli.add_command(train, "t")
 cli.add_command(predict, "p")
 cli.add_command(segment, "s")
+cli.add_command(_evaluate, "eval")
 
 if __name__ == "__main__":
     cli()

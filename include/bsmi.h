@@ -440,6 +440,51 @@ int bsmi_seg_set_host_flood(bsmi_seg *h, int on);
  * After an overflow the outputs of that call are undefined. */
 int bsmi_seg_status(bsmi_seg *h, void *stream);
 
+/* ---- evaluation ---- */
+/* `bs evaluate` (evaluate.py:39-101): affinity error maps of a segmentation against the network's own affinities
+ * (eval/compute_errors.py:25-223, gp/add_aff_errors.py) and the (gt, seg) contingency table behind Rand / VOI
+ * (eval/compute_metrics.py:73-122, funlib.evaluate.rand_voi).  The handle holds the pair table (three open-addressing tables
+ * of pair_capacity slots: gt ids, seg ids, (gt slot, seg slot) pairs with u64 counts), an overflow flag, and the f32 scratch of
+ * the error pass (grown on demand; growing synchronises the stream).  pair_capacity: a power of two in [2, 2^31]. */
+typedef struct bsmi_eval bsmi_eval;
+int bsmi_eval_create(int device, uint64_t pair_capacity, bsmi_eval **out);
+int bsmi_eval_destroy(bsmi_eval *h);
+
+/* Affinity errors of a tile of Scan chunks (a layer of chunks across the ROI, or more), AddAffErrors._create_diff /
+ * _create_mask with the per-chunk normalisation, in the reference's f32 arithmetic (no contraction):
+ *   s_e  = seg[v] == seg[v + offset_e] && seg[v] != 0;  p_e = float(pred[e][v]) * float(1/255)
+ *   diff = ((s_0 - p_0)^2 + (s_1 - p_1)^2) + ...  (* float(mask[v]) when mask_dev is given)
+ *   d    = diff / max(diff over the chunk) (0 when that is 0);  error_map = u8(trunc(d * 255));  error_mask = floor < d < ceil
+ * tile_shape (tz, ty, tx): the tile; pred_dev u8 [n_channels][tz][ty][tx], mask_dev u8 [tz][ty][tx] or NULL, the two outputs
+ * u8 [tz][ty][tx].  seg_dev u64 [seg_shape]: the segmentation around the tile, seg_origin = position of its first voxel relative
+ * to the tile's first voxel (<= 0); it must hold every v + offset_e (zeros where the dataset ends), else BSMI_ERR_INVALID.
+ * offsets: host int32 [n_channels][3] (n_channels <= 16), either sign.  chunk_shape: the chunk's extent per axis (clamped
+ * to the tile): along each axis chunks start at 0, c, 2c, ... and the last one is moved back to end at the tile's end; a voxel
+ * takes the value of the last chunk covering it.  At most 65535 chunks per tile.  hist_dev u64 [257] accumulates (not cleared): [i] +=
+ * voxels with error_map == i, [256] += voxels with error_mask == 1, over the slices z < count_z_end only (the caller's next
+ * layer rewrites the rest).  25 bytes of HBM per voxel at 6 channels with a mask (f32 diff stored between two kernels). */
+int bsmi_eval_aff_errors_u8(bsmi_eval *h, const uint64_t *seg_dev, const int64_t seg_shape[3], const int64_t seg_origin[3],
+                            const uint8_t *pred_dev, int n_channels, const int64_t tile_shape[3], const uint8_t *mask_dev,
+                            const int32_t *offsets, const int64_t chunk_shape[3], float floor_, float ceil_, int64_t count_z_end,
+                            uint8_t *error_map_dev, uint8_t *error_mask_dev, uint64_t *hist_dev, void *stream);
+
+/* Adds a tile's (gt, seg) voxel pairs to the handle's pair table (reset != 0 empties it first).  gt_dev, seg_dev u64
+ * [shape]; mask_dev u8 [shape] or NULL: both ids are multiplied by the mask value first, wrapping at 2^64, as the reference
+ * does.  Voxels whose (masked) gt id is 0 are left out; seg id 0 is an ordinary label.  Runs of equal pairs along x are
+ * counted within a wave before the atomics; counts are exact, so the table does not depend on the order of the atomics.
+ * A full table sets the overflow flag (bsmi_eval_status); the counts are then incomplete. */
+int bsmi_eval_pairs_u64(bsmi_eval *h, const uint64_t *gt_dev, const uint64_t *seg_dev, const uint8_t *mask_dev,
+                        const int64_t shape[3], int reset, void *stream);
+
+/* Reads the pair table out: (gt_out_dev[i], seg_out_dev[i], count_out_dev[i]) for i < *n_dev (u64 on the device), in no
+ * particular order.  More than out_capacity pairs set the overflow flag. */
+int bsmi_eval_pairs_read(bsmi_eval *h, uint64_t *gt_out_dev, uint64_t *seg_out_dev, uint64_t *count_out_dev,
+                         uint64_t out_capacity, uint64_t *n_dev, void *stream);
+
+/* BSMI_OK, or BSMI_ERR_OVERFLOW if a table of this handle overflowed since the previous call (the flag is cleared here).
+ * Synchronises `stream`. */
+int bsmi_eval_status(bsmi_eval *h, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,11 @@ def _load():
         "bsmi_train_affinity_targets": (i32, [C.c_int, vp, vp, i64p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, vp, vp, vp]),
         "bsmi_train_lsd_targets": (i32, [C.c_int, vp, vp, i64p, i64p, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, vp, vp, vp]),
+        "bsmi_train_lsd2d_targets": (i32, [C.c_int, vp, vp, C.c_int, i64p, i64p, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int,
+                                           vp, vp, vp]),
+        "bsmi_train_affinity_targets_roi": (i32, [C.c_int, vp, vp, C.c_int, i64p, i64p, i64p, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                                  C.c_int, C.c_float, C.c_float, vp, vp, vp]),
+        "bsmi_train_mask_sat": (i32, [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]),
         "bsmi_unet_set_persistent_grid": (i32, [p, C.c_int]),
         "bsmi_unet_profile_executed": (i32, [p, C.POINTER(C.c_double), C.c_int]),
         "bsmi_debug_lds_canary": (i32, [i32, i32, i32, vp, vp]),

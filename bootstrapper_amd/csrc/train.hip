@@ -1861,6 +1861,59 @@ __global__ void balance_kernel(const float* __restrict__ affs, float* __restrict
     weights[i] = weights[i] * (affs[i] > 0.f ? w_pos : w_neg);
 }
 
+// affinities of the output ROI of label arrays grown by the neighbourhood's context (bsmi_train_affinity_targets_roi)
+// blockIdx.y = sample; affs / mask [n][S][d][h][w]; counts[2 s] masked, counts[2 s + 1] masked positives of sample s
+__global__ void affinity_roi_kernel(const int64_t* __restrict__ labels, const uint8_t* __restrict__ unl, Neighborhood nb, int S, int D,
+                                    int H, int W, int oz, int oy, int ox, int d, int h, int w, float* __restrict__ affs, float* __restrict__ mask,
+                                    unsigned long long* __restrict__ counts) {
+  const int s = blockIdx.y;
+  const size_t nroi = (size_t)d * h * w, nall = (size_t)S * nroi, sample = (size_t)D * H * W;
+  const int64_t* lab = labels + (size_t)s * sample;
+  const uint8_t* un = unl ? unl + (size_t)s * sample : nullptr;
+  unsigned long long n_mask = 0, n_pos = 0;
+  for (size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x; r < nroi; r += (size_t)gridDim.x * blockDim.x) {
+    const int x = (int)(r % w) + ox, y = (int)((r / w) % h) + oy, z = (int)(r / ((size_t)w * h)) + oz;
+    const size_t p = ((size_t)z * H + y) * W + x;
+    const int64_t a = lab[p];
+    const bool known = !un || un[p];
+    for (int e = 0; e < nb.n; ++e) {
+      const int zz = z + nb.off[e][0], yy = y + nb.off[e][1], xx = x + nb.off[e][2];
+      const bool inside = zz >= 0 && zz < D && yy >= 0 && yy < H && xx >= 0 && xx < W;
+      float aff = 0.f, m = 0.f;
+      if (inside) {
+        const int64_t b = lab[((size_t)zz * H + yy) * W + xx];
+        aff = (a == b && a > 0) ? 1.f : 0.f;
+        m = known ? 1.f : 0.f;
+      }
+      const size_t o = (size_t)e * nall + (size_t)s * nroi + r;
+      affs[o] = aff;
+      mask[o] = m;
+      n_mask += m > 0.f;
+      n_pos += (m > 0.f && aff > 0.f);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    n_mask += __shfl_down(n_mask, o);
+    n_pos += __shfl_down(n_pos, o);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&counts[2 * s], n_mask);
+    atomicAdd(&counts[2 * s + 1], n_pos);
+  }
+}
+
+__global__ void balance_roi_kernel(const float* __restrict__ affs, float* __restrict__ weights, size_t total, size_t nroi, int S,
+                                   const unsigned long long* __restrict__ counts, float clip_min, float clip_max) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int s = (int)((i / nroi) % S);
+    const float n_mask = fmaxf((float)counts[2 * s], 1.f);
+    float frac = (float)counts[2 * s + 1] / n_mask;
+    frac = fminf(fmaxf(frac, clip_min), clip_max);
+    const float w_pos = 1.f / (2.f * frac), w_neg = 1.f / (2.f * (1.f - frac));
+    weights[i] = weights[i] * (affs[i] > 0.f ? w_pos : w_neg);
+  }
+}
+
 }  // namespace bsmi
 
 extern "C" {
@@ -2528,6 +2581,54 @@ int bsmi_train_affinity_targets(int device, int64_t* labels_dev, const uint8_t* 
   const size_t total = nvox * (size_t)n;
   hipLaunchKernelGGL(balance_kernel, dim3((unsigned)std::min<size_t>((total + bs - 1) / bs, 65535)), dim3(bs), 0, s, affs_dev, weights_dev, total,
                      counts, clip_min, clip_max);
+  BSMI_HIP(hipGetLastError());
+  BSMI_HIP(hipFreeAsync(grown, s));
+  return BSMI_OK;
+}
+
+int bsmi_train_affinity_targets_roi(int device, int64_t* labels_dev, const uint8_t* unlabelled_dev, int n_samples, const int64_t shape[3],
+                                    const int64_t roi_offset[3], const int64_t roi_shape[3], const int32_t* neighborhood, int n,
+                                    int grow_steps, int only_xy, float clip_min, float clip_max, float* affs_dev, float* weights_dev,
+                                    void* stream) {
+  if (!labels_dev || !shape || !roi_offset || !roi_shape || !neighborhood || !affs_dev || !weights_dev) BSMI_FAIL(BSMI_ERR_INVALID, "null argument");
+  if (n < 1 || n > kMaxNeighborhood) BSMI_FAIL(BSMI_ERR_INVALID, "neighborhood of %d offsets (1..%d supported)", n, kMaxNeighborhood);
+  if (grow_steps < 0 || grow_steps > 16) BSMI_FAIL(BSMI_ERR_INVALID, "grow_steps %d outside 0..16", grow_steps);
+  if (n_samples < 1 || n_samples > 65535) BSMI_FAIL(BSMI_ERR_INVALID, "n_samples %d outside 1..65535", n_samples);
+  for (int d = 0; d < 3; ++d) {
+    if (shape[d] < 1 || shape[d] > 65536) BSMI_FAIL(BSMI_ERR_INVALID, "bad shape");
+    if (roi_shape[d] < 1 || roi_offset[d] < 0 || roi_offset[d] + roi_shape[d] > shape[d]) BSMI_FAIL(BSMI_ERR_INVALID, "ROI outside the label array");
+  }
+  const int S = n_samples, D = (int)shape[0], H = (int)shape[1], W = (int)shape[2];
+  const size_t nvox = (size_t)S * D * H * W, nroi = (size_t)roi_shape[0] * roi_shape[1] * roi_shape[2];
+  if (nvox > ((size_t)1 << 40) || (int64_t)S * D > INT32_MAX) BSMI_FAIL(BSMI_ERR_INVALID, "bad shape");
+  Neighborhood nb;
+  nb.n = n;
+  for (int e = 0; e < n; ++e)
+    for (int d = 0; d < 3; ++d) nb.off[e][d] = neighborhood[3 * e + d];
+  BSMI_HIP(hipSetDevice(device));
+  hipStream_t s = (hipStream_t)stream;
+  // scratch on the stream: the grown labels (the erosion reads its neighbours' old values) and two counters per sample
+  int64_t* grown = nullptr;
+  BSMI_HIP(hipMallocAsync((void**)&grown, nvox * sizeof(int64_t) + 2 * (size_t)S * sizeof(unsigned long long), s));
+  unsigned long long* counts = (unsigned long long*)(grown + nvox);
+  BSMI_HIP(hipMemsetAsync(counts, 0, 2 * (size_t)S * sizeof(unsigned long long), s));
+  const int bs = 256;
+  const unsigned ggrid = (unsigned)std::min<size_t>((nvox + bs - 1) / bs, 65535);
+  if (only_xy)  // sections never see each other: the samples' sections are one stack
+    hipLaunchKernelGGL(grow_boundary_kernel, dim3(ggrid), dim3(bs), 0, s, labels_dev, unlabelled_dev, grown, S * D, H, W, grow_steps, 1);
+  else
+    for (int i = 0; i < S; ++i) {
+      const size_t o = (size_t)i * D * H * W;
+      hipLaunchKernelGGL(grow_boundary_kernel, dim3(ggrid), dim3(bs), 0, s, labels_dev + o, unlabelled_dev ? unlabelled_dev + o : nullptr,
+                         grown + o, D, H, W, grow_steps, 0);
+    }
+  BSMI_HIP(hipMemcpyAsync(labels_dev, grown, nvox * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(affinity_roi_kernel, dim3((unsigned)std::min<size_t>((nroi + bs - 1) / bs, 4096), (unsigned)S), dim3(bs), 0, s, grown,
+                     unlabelled_dev, nb, S, D, H, W, (int)roi_offset[0], (int)roi_offset[1], (int)roi_offset[2], (int)roi_shape[0],
+                     (int)roi_shape[1], (int)roi_shape[2], affs_dev, weights_dev, counts);
+  const size_t total = nroi * S * (size_t)n;
+  hipLaunchKernelGGL(balance_roi_kernel, dim3((unsigned)std::min<size_t>((total + bs - 1) / bs, 65535)), dim3(bs), 0, s, affs_dev, weights_dev,
+                     total, nroi, S, counts, clip_min, clip_max);
   BSMI_HIP(hipGetLastError());
   BSMI_HIP(hipFreeAsync(grown, s));
   return BSMI_OK;

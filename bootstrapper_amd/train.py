@@ -9,7 +9,9 @@ What is NOT restated: the gunpowder augmentation chain of models/3d_affs/train.p
 DeformAugment, ShiftAugment, noise / intensity / gamma / impulse / smooth / defect augmentations) and the snapshot
 callback -- third-party pipeline code outside the hot path.  `SampleSource` does the deterministic part only: random
 location with the >= 5 % labelled-voxel rejection, Normalize + IntensityScaleShift(2, -1), then GrowBoundary,
-AddAffinities on the configured neighbourhood and BalanceLabels in one device call (`affinity_targets`).  The arithmetic of the step itself is libbsmi (csrc/train.hip).
+AddAffinities on the configured neighbourhood and BalanceLabels in one device call (`affinity_targets`).  `SectionSource`
+does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
+of each section in one launch each (csrc/train2d.hip).  The arithmetic of the step itself is libbsmi (csrc/train.hip).
 """
 import ctypes as C
 import glob
@@ -87,6 +89,220 @@ def lsd_targets(labels, roi_offset, roi_shape, sigma, voxel_size, downsample=1, 
         (C.c_float * 3)(*[float(v) for v in voxel_size]), int(downsample), C.c_void_p(out.data_ptr()), C.c_void_p(weights.data_ptr()),
         C.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)))
     return out, weights
+
+
+def lsd2d_targets(labels, roi_offset, roi_shape, sigma, voxel_size, downsample=1, unlabelled=None):
+    """2-D local shape descriptors of a stack of sections in one launch (reference models/2d_mtlsd/train.py: Add2DLSDs).
+    labels: int64 CUDA (S, H, W) holding the sections with the window context; roi_offset / roi_shape: (y, x);
+    sigma / voxel_size: (y, x) world units.  -> (gt_lsds, lsds_weights) float32 (6, S, h, w)."""
+    if labels.dtype != torch.int64 or not labels.is_cuda or labels.dim() != 3 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 CUDA tensor (S, H, W)")
+    if unlabelled is not None and (unlabelled.dtype != torch.uint8 or unlabelled.shape != labels.shape or not unlabelled.is_contiguous()):
+        raise ValueError("unlabelled must be a contiguous uint8 tensor of the labels' shape")
+    sig = [float(sigma)] * 2 if isinstance(sigma, (int, float)) else [float(v) for v in sigma]
+    n = int(labels.shape[0])
+    out = torch.empty((6, n) + tuple(int(v) for v in roi_shape), dtype=torch.float32, device=labels.device)
+    weights = torch.empty_like(out)
+    _lib.check(_lib.lib.bsmi_train_lsd2d_targets(
+        labels.device.index, C.c_void_p(labels.data_ptr()), C.c_void_p(unlabelled.data_ptr()) if unlabelled is not None else None, n,
+        (C.c_int64 * 2)(*labels.shape[1:]), (C.c_int64 * 2)(*[int(v) for v in roi_offset]), (C.c_int64 * 2)(*[int(v) for v in roi_shape]),
+        (C.c_float * 2)(*sig), (C.c_float * 2)(*[float(v) for v in voxel_size]), int(downsample), C.c_void_p(out.data_ptr()),
+        C.c_void_p(weights.data_ptr()), C.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)))
+    return out, weights
+
+
+def affinity_targets_roi(labels, unlabelled, roi_offset, roi_shape, neighborhood, grow_steps=0, only_xy=True, clip=(0.05, 0.95)):
+    """GrowBoundary -> AddAffinities -> BalanceLabels of S independent label arrays that carry the neighbourhood's context
+    (bsmi_train_affinity_targets_roi): affinities of the ROI only, balanced per array over its ROI.
+    labels: int64 CUDA (S, D, H, W), overwritten with the grown-boundary labels; unlabelled: uint8 CUDA of that shape or None;
+    roi_offset / roi_shape: (z, y, x).  Returns (gt_affs, affs_weights), float32 (n, S, d, h, w)."""
+    if labels.dtype != torch.int64 or not labels.is_cuda or labels.dim() != 4 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 CUDA tensor (S, D, H, W)")
+    if unlabelled is not None and (unlabelled.dtype != torch.uint8 or unlabelled.shape != labels.shape or not unlabelled.is_contiguous()):
+        raise ValueError("unlabelled must be a contiguous uint8 tensor of the labels' shape")
+    n = len(neighborhood)
+    nb = (C.c_int32 * (3 * n))(*[int(v) for off in neighborhood for v in off])
+    s = int(labels.shape[0])
+    affs = torch.empty((n, s) + tuple(int(v) for v in roi_shape), dtype=torch.float32, device=labels.device)
+    weights = torch.empty_like(affs)
+    _lib.check(_lib.lib.bsmi_train_affinity_targets_roi(
+        labels.device.index, C.c_void_p(labels.data_ptr()), C.c_void_p(unlabelled.data_ptr()) if unlabelled is not None else None, s,
+        _lib.i64x3(labels.shape[1:]), _lib.i64x3(roi_offset), _lib.i64x3(roi_shape), nb, n, int(grow_steps), 1 if only_xy else 0,
+        float(clip[0]), float(clip[1]), C.c_void_p(affs.data_ptr()), C.c_void_p(weights.data_ptr()),
+        C.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)))
+    return affs, weights
+
+
+def mask_sat(mask):
+    """Summed-area table of mask sections on the device (bsmi_train_mask_sat): mask uint8 CUDA (S, H, W) -> int32 CUDA
+    (S, H + 1, W + 1) holding the u32 counts (a section of fewer than 2^31 voxels keeps them non-negative)."""
+    if mask.dtype != torch.uint8 or not mask.is_cuda or mask.dim() != 3 or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous uint8 CUDA tensor (S, H, W)")
+    s, h, w = (int(v) for v in mask.shape)
+    sat = torch.empty((s, h + 1, w + 1), dtype=torch.int32, device=mask.device)
+    _lib.check(_lib.lib.bsmi_train_mask_sat(mask.device.index, C.c_void_p(mask.data_ptr()), s, h, w, C.c_void_p(sat.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream(mask.device).cuda_stream)))
+    return sat
+
+
+def _read_world(ds, world_lo, shape, dtype):
+    """ds[world_lo : world_lo + shape voxels] on ds's grid (world_lo in world units), zeros beyond the array (gp.Pad(x, None))."""
+    vs, off = list(ds.voxel_size), list(ds.offset)
+    nd = len(vs)
+    lo = []
+    for w, o, v in zip(world_lo, off, vs):
+        if (w - o) % v:
+            raise ValueError(f"{ds.path if hasattr(ds, 'path') else 'dataset'}: position {world_lo} is not on its voxel grid (offset {off}, voxel size {vs})")
+        lo.append((w - o) // v)
+    out = np.zeros(shape, dtype=dtype)
+    full = ds.shape[-nd:]
+    src, dst = [], []
+    for a, n, m in zip(lo, shape, full):
+        b0, b1 = max(a, 0), min(a + n, m)
+        if b1 <= b0:
+            return out
+        src.append(slice(b0, b1))
+        dst.append(slice(b0 - a, b1 - a))
+    out[tuple(dst)] = ds[tuple(src)]
+    return out
+
+
+class SectionSource:
+    """Infinite iterator of reference-style batches of the 2-D setups (models/2d_mtlsd/train.py:29-164, 2d_lsd, 2d_affs):
+    `batch_size` independent draws of one output section each, stacked along the depth axis the training step reads.
+
+    A draw picks a sample, then (z, y, x) of its output window inside the labels volume (one Generator, seed 42 + rank), and is
+    rejected until at least 5 % of the window is known (gp.Reject(mask=unlabelled, min_masked=0.05); unlabelled = the mask
+    dataset, else labels > 0).  The test is four lookups in a summed-area table of the mask, built on the device once per
+    sample; only the sections that hold an acceptable window keep theirs (as uint32 on the host), so a store with one painted
+    section in a hundred costs a hundredth of its voxels, and the draw loop never gives up while a window exists.
+    Raw and mask are read at the labels' world position (their own offsets: ArraySource + MergeProvider), zeros beyond them.
+    Batch: raw (in_channels * adj_slices, S, H, W) normalised to [-1, 1]; gt_lsds / lsds_weights (6, S, h, w);
+    gt_affs / affs_weights (K, S, h, w)."""
+
+    def __init__(self, samples, input_shape, output_shape, adj_slices=1, device=0, seed=42, batch_size=10, lsds=None, affs=None):
+        """lsds: {"sigma", "downsample"} of net_config outputs.2d_lsds, or None; affs: {"neighborhood" (2-D offsets),
+        "grow_boundary"} of outputs.2d_affs, or None."""
+        if lsds is None and affs is None:
+            raise ValueError("a 2-D setup has a 2d_lsds and / or a 2d_affs output")
+        self.samples = [(open_ds(s["raw"]), open_ds(s["labels"]), open_ds(s["mask"]) if s.get("mask") else None) for s in samples]
+        self.inp, self.out = tuple(int(v) for v in input_shape), tuple(int(v) for v in output_shape)
+        self.adj = int(adj_slices)
+        self.dev = torch.device("cuda", device)
+        self.rng = np.random.default_rng(seed)
+        self.batch_size = int(batch_size)
+        self.lsds, self.affs = lsds, affs
+        self.ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
+        lo, hi = [0, 0], [0, 0]
+        if lsds is not None:
+            self.df = int(lsds.get("downsample", 1))
+            sig = lsds["sigma"]
+            self.sigma = [float(sig)] * 2 if isinstance(sig, (int, float)) else [float(v) for v in sig]
+            if any(o % self.df for o in self.out):
+                raise ValueError(f"output_shape {list(self.out)} must be a multiple of the LSD downsample factor {self.df}")
+        if affs is not None:
+            self.nhood = [[0] + [int(v) for v in off] for off in affs["neighborhood"][: int(affs["dims"])]]
+            self.grow = int(affs.get("grow_boundary", 0))
+            # AddAffinities grows the labels request by the neighbourhood (negative offsets before, positive after)
+            for d in range(2):
+                lo[d] = max(0, -min(off[d + 1] for off in self.nhood))
+                hi[d] = max(0, max(off[d + 1] for off in self.nhood))
+        self.aff_lo, self.aff_hi = lo, hi
+        self.vs = tuple(self.samples[0][1].voxel_size)
+        for raw_ds, lab_ds, mask_ds in self.samples:
+            if any(tuple(ds.voxel_size) != self.vs for ds in (raw_ds, lab_ds, mask_ds) if ds is not None):
+                raise ValueError(f"raw, labels and mask of every sample must share one voxel size ({list(self.vs)})")
+        # AddLocalShapeDescriptor.prepare: 3 sigma of context in y and x (sigma_z = 0), snapped to the sub-sampling grid
+        self.lsd_ctx = [-(-int(-(-3.0 * s // v)) // self.df) * self.df for s, v in zip(self.sigma, self.vs[1:])] if lsds is not None else [0, 0]
+        # one labels crop per draw serves both: the larger context on each side
+        self.lo = [max(a, b) for a, b in zip(self.lsd_ctx, lo)]
+        self.hi = [max(a, b) for a, b in zip(self.lsd_ctx, hi)]
+        self.tables = [None] * len(self.samples)
+
+    def _known(self, i, start, shape):
+        """known-voxel mask (uint8) of the labels voxels [start, start + shape) of sample i, zeros beyond the volume"""
+        _, lab_ds, mask_ds = self.samples[i]
+        world = [o + a * v for o, a, v in zip(lab_ds.offset, start, lab_ds.voxel_size)]
+        src = mask_ds if mask_ds is not None else lab_ds
+        return (_read_world(src, world, tuple(shape), src.dtype) > 0).astype(np.uint8)
+
+    def _tables(self, i):
+        """{z: uint32 (H + 1, W + 1) summed-area table} of the sections of sample i that hold an acceptable window"""
+        if self.tables[i] is None:
+            _, lab_ds, mask_ds = self.samples[i]
+            D, H, W = lab_ds.shape[-3:]
+            h, w = self.out
+            if H < h or W < w:
+                raise ValueError("labels volume smaller than the network's output section")
+            need = -(-5 * h * w // 100)   # >= 5 % of the window
+            tables = {}
+            step = max(1, min(D, (64 << 20) // max(1, H * W)))   # sections per device pass
+            for z0 in range(0, D, step):
+                nz = min(step, D - z0)
+                m = torch.from_numpy(self._known(i, (z0, 0, 0), (nz, H, W))).to(self.dev)
+                sat = mask_sat(m)
+                totals = sat[:, H, W].cpu().numpy()
+                for k in np.nonzero(totals >= need)[0]:
+                    t = sat[int(k)].cpu().numpy().view(np.uint32).astype(np.int64)
+                    win = t[h:, w:] - t[:-h, w:] - t[h:, :-w] + t[:-h, :-w]
+                    if win.max() >= need:
+                        tables[z0 + int(k)] = t.astype(np.uint32)
+            self.tables[i] = tables
+        return self.tables[i]
+
+    def __iter__(self):
+        return self
+
+    def _draw(self):
+        h, w = self.out
+        need = -(-5 * h * w // 100)
+        if not any(self._tables(i) for i in range(len(self.samples))):
+            raise RuntimeError("no training location with at least 5 % labelled voxels in any sample")
+        while True:
+            i = int(self.rng.integers(len(self.samples)))
+            shape = self.samples[i][1].shape[-3:]
+            z, y, x = (int(self.rng.integers(0, s - o + 1)) for s, o in zip(shape, (1, h, w)))
+            t = self._tables(i).get(z)
+            if t is None:
+                continue
+            cnt = int(t[y + h, x + w]) - int(t[y, x + w]) - int(t[y + h, x]) + int(t[y, x])
+            if cnt >= need:
+                return i, z, y, x
+
+    def __next__(self):
+        draws = [self._draw() for _ in range(self.batch_size)]
+        h, w = self.out
+        H, W = self.inp
+        lo, hi = self.lo, self.hi
+        big = (1, h + lo[0] + hi[0], w + lo[1] + hi[1])
+        raw = np.zeros((self.adj, len(draws), H, W), dtype=np.uint8)
+        lab = np.zeros((len(draws),) + big[1:], dtype=np.int64)
+        unl = np.zeros((len(draws),) + big[1:], dtype=np.uint8)
+        for s, (i, z, y, x) in enumerate(draws):
+            raw_ds, lab_ds, _ = self.samples[i]
+            vs, off = lab_ds.voxel_size, lab_ds.offset
+            # raw: the section and its neighbours with the network's context, at the labels' world position
+            world = [off[0] + (z - self.adj // 2) * vs[0], off[1] + (y - self.ctx[0]) * vs[1], off[2] + (x - self.ctx[1]) * vs[2]]
+            raw[:, s] = _read_world(raw_ds, world, (self.adj, H, W), np.uint8)
+            start = (z, y - lo[0], x - lo[1])
+            world = [o + a * v for o, a, v in zip(off, start, vs)]
+            lab[s] = _read_world(lab_ds, world, big, lab_ds.dtype)[0].astype(np.int64)
+            unl[s] = self._known(i, start, big)[0]
+        batch = {"raw": torch.from_numpy(raw).to(self.dev).float() * (1.0 / 255.0) * 2.0 - 1.0}
+        lab_t = torch.from_numpy(lab).to(self.dev)
+        unl_t = torch.from_numpy(unl).to(self.dev)
+        if self.lsds is not None:
+            c = self.lsd_ctx
+            ys, xs = slice(lo[0] - c[0], lo[0] + h + c[0]), slice(lo[1] - c[1], lo[1] + w + c[1])
+            lsds, lw = lsd2d_targets(lab_t[:, ys, xs].contiguous(), c, self.out, self.sigma, self.vs[1:], self.df, unl_t[:, ys, xs].contiguous())
+            batch.update(gt_lsds=lsds, lsds_weights=lw)
+        if self.affs is not None:
+            a, b = self.aff_lo, self.aff_hi
+            ys, xs = slice(lo[0] - a[0], lo[0] + h + b[0]), slice(lo[1] - a[1], lo[1] + w + b[1])
+            affs, aw = affinity_targets_roi(lab_t[:, None, ys, xs].contiguous(), unl_t[:, None, ys, xs].contiguous(), (0, a[0], a[1]),
+                                            (1, h, w), self.nhood, self.grow, only_xy=True)
+            batch.update(gt_affs=affs[:, :, 0], affs_weights=aw[:, :, 0])
+        return batch
 
 
 class SampleSource:
@@ -223,13 +439,47 @@ class PrefetchSource:
         self.thread.join(timeout=5)
 
 
+BATCH_2D = 10   # models/2d_*/train.py: batch_size = 10 sections per step (gp.Stack)
+
+
+def setup_name(net_config):
+    """The reference's setup directory name of a net_config: 2d_mtlsd, 3d_affs_from_2d_lsd, ..."""
+    def name(keys):
+        dim = "2d" if any(k.startswith("2d") for k in keys) else "3d"
+        kinds = {k.split("_", 1)[1] for k in keys}
+        return f"{dim}_" + ("mtlsd" if kinds == {"affs", "lsds"} else ("lsd" if kinds == {"lsds"} else "affs"))
+    out = name(net_config["outputs"])
+    if set(net_config.get("inputs", {"raw": None})) == {"raw"}:
+        return out
+    return f"{out}_from_{name(net_config['inputs'])}"
+
+
+def training_settings(net_config):
+    """What a training step of this setup is: {"two_d", "batch_size", "in_shape", "lr"}.  2-D setups train on a stack of
+    BATCH_2D sections, (S, H, W) for the lifted net, with Adam at lr 1e-4 (models/2d_mtlsd/train.py:194, 2d_lsd:154,
+    2d_affs:161); the 3-D ones on one block at 0.5e-4 (models/3d_affs/train.py)."""
+    dfs = net_config["downsample_factors"]
+    two_d = bool(dfs) and len(dfs[0]) == 2
+    inp = [int(v) for v in net_config["input_shape"]]
+    if two_d:
+        return {"two_d": True, "batch_size": BATCH_2D, "in_shape": (BATCH_2D, *inp), "lr": 1.0e-4}
+    return {"two_d": False, "batch_size": 1, "in_shape": tuple(inp), "lr": 0.5e-4}
+
+
 def make_sample_source(config, net_config, device=0, rank=0):
     """The built-in sample stream of `bs train` for this rank: seed 42 + rank, so that data-parallel ranks see different
     samples (with one seed for all, the averaged gradient would be the single-rank gradient computed N times)."""
     outs = net_config["outputs"]
+    if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
+        raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
+                                  "the built-in sample source does not make; it feeds 2d_affs, 2d_lsd, 2d_mtlsd, 3d_affs, 3d_lsd and 3d_mtlsd")
+    if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
+        s = training_settings(net_config)
+        return SectionSource(config["samples"], net_config["input_shape"], net_config["output_shape"], int(net_config.get("adj_slices", 1)),
+                             device=device, seed=42 + int(rank), batch_size=s["batch_size"], lsds=outs.get("2d_lsds"), affs=outs.get("2d_affs"))
     out3d, lsd3d = outs.get("3d_affs"), outs.get("3d_lsds")
     if set(outs) - {"3d_affs", "3d_lsds"} or not outs:
-        raise NotImplementedError(f"the built-in sample source feeds the 3-D setups (3d_affs, 3d_lsd, 3d_mtlsd), not {sorted(outs)}")
+        raise NotImplementedError(f"the built-in sample source feeds the 2-D and 3-D setups, not the outputs {sorted(outs)}")
     head = "mtlsd" if out3d and lsd3d else ("affs" if out3d else "lsds")
     nhood = out3d["neighborhood"][: int(out3d["dims"])] if out3d else [[-1, 0, 0], [0, -1, 0], [0, 0, -1]]
     return SampleSource(config["samples"], net_config["input_shape"], net_config["output_shape"], nhood, device=device,
@@ -241,13 +491,15 @@ def make_sample_source(config, net_config, device=0, rank=0):
 def default_init(net_config, seed=42):
     """torch's default Conv3d initialisation (kaiming_uniform(a=sqrt(5)), bias uniform(+-1/sqrt(fan_in))) for every
     parameter of the reference Model, keyed like its state_dict."""
-    from .unet import HEAD_OF_OUTPUT
+    from .unet import HEAD_OF_OUTPUT, input_channels
     g = torch.Generator().manual_seed(seed)
     nf, inc = int(net_config["num_fmaps"]), int(net_config["fmap_inc_factor"])
     dfs = net_config["downsample_factors"]
     nl = len(dfs) + 1
-    ksd = net_config.get("kernel_size_down") or [[[3, 3, 3], [3, 3, 3]]] * nl
-    ksu = net_config.get("kernel_size_up") or [[[3, 3, 3], [3, 3, 3]]] * (nl - 1)
+    nd = len(dfs[0]) if dfs else 3   # 2-D setups: Conv2d (O, I, kh, kw) parameters, the first reading in_channels * adj_slices
+    k3, one = [3] * nd, (1,) * nd
+    ksd = net_config.get("kernel_size_down") or [[k3, k3]] * nl
+    ksu = net_config.get("kernel_size_up") or [[k3, k3]] * (nl - 1)
     sd = {}
 
     def conv(key, cout, cin, k):
@@ -261,14 +513,14 @@ def default_init(net_config, seed=42):
         for i, k in enumerate(kernels):
             conv(f"{prefix}.conv_pass.{2 * i}", cout, c, k)
             c = cout
-        conv(f"{prefix}.residual.0", cout, cin, (1, 1, 1))
+        conv(f"{prefix}.residual.0", cout, cin, one)
 
     for lvl in range(nl):
-        conv_pass(f"unet.l_conv.{lvl}", int(net_config["in_channels"]) if lvl == 0 else nf * inc ** (lvl - 1), nf * inc ** lvl, ksd[lvl])
+        conv_pass(f"unet.l_conv.{lvl}", input_channels(net_config) if lvl == 0 else nf * inc ** (lvl - 1), nf * inc ** lvl, ksd[lvl])
     for lvl in range(nl - 1):
         conv_pass(f"unet.r_conv.0.{lvl}", nf * inc ** lvl + nf * inc ** (lvl + 1), nf * inc ** lvl, ksu[lvl])
     for name, val in net_config["outputs"].items():
-        conv_pass(HEAD_OF_OUTPUT[name], nf, int(val["dims"]), [(1, 1, 1)])
+        conv_pass(HEAD_OF_OUTPUT[name], nf, int(val["dims"]), [one])
     return sd
 
 
@@ -303,7 +555,8 @@ def run_training(config_file, device=0, batches=None, log=print):
         model.load_state_dict(default_init(net_config, seed=42))
     # `arithmetic`, `deterministic` (additions to the reference's train config): "split-bf16" (default) or "f32"; ordered
     # reductions so that two runs from the same state give the same bits (default false), see training.Trainer
-    trainer = Trainer(model, net_config["input_shape"], arithmetic=config.get("arithmetic", "split-bf16"),
+    settings = training_settings(net_config)
+    trainer = Trainer(model, settings["in_shape"], lr=settings["lr"], arithmetic=config.get("arithmetic", "split-bf16"),
                       deterministic=bool(config.get("deterministic", False)))
     if ckpt and load_optimizer_state(trainer, ckpt):
         log(f"optimizer state restored (step {trainer.step_count()})")

@@ -134,6 +134,16 @@ def save_snapshot(setup_dir, voxel_size, step, rank, data):
     return path
 
 
+def stacked_sections(data):
+    """A 2-D batch as the reference's gp.Stack holds it: the section stack (C, S, ...) of the training step with the batch
+    axis first; raw (S, C, H, W), targets, weights and predictions (S, C, 1, h, w) (stack_infer=True adds the z axis)."""
+    out = {}
+    for k, v in data.items():
+        v = v.transpose(0, 1)
+        out[k] = v if k == "raw" else v[:, :, None]
+    return out
+
+
 def fit(trainer, batches, max_iterations, save_checkpoints_every=0, setup_dir=None, log_every=10, log=print, start_iteration=0,
         save_snapshots_every=0, voxel_size=None):
     """The training loop of training.py:96-137 without Lightning: `batches` is any iterable of reference-style batch
@@ -167,6 +177,8 @@ def fit(trainer, batches, max_iterations, save_checkpoints_every=0, setup_dir=No
         if save_snapshots_every and setup_dir and voxel_size is not None and (it == 1 or it % save_snapshots_every == 0):
             data = dict(batch)
             data.update(trainer.predictions())
+            if trainer.model.two_d:
+                data = stacked_sections(data)
             save_snapshot(setup_dir, voxel_size, it, rank, data)
         if save_checkpoints_every and setup_dir and it % save_checkpoints_every == 0:
             rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
@@ -190,7 +202,9 @@ _COMM_STREAMS = {}
 
 class Trainer:
     def __init__(self, model, in_shape, lr=0.5e-4, betas=(0.9, 0.999), eps=1e-8, arithmetic="split-bf16", deterministic=False):
-        """model: bootstrapper_amd.unet.Model with weights loaded; in_shape: (D, H, W) of the training block.
+        """model: bootstrapper_amd.unet.Model with weights loaded; in_shape: (D, H, W) of the training block -- for a 2-D
+        setup (S, H, W): S sections trained as one stack (the net is lifted to (1, k, k) kernels and (1, 2, 2) pools, so
+        depth never mixes sections, and the masked mean over the stack is the reference's loss over its batch of S).
         arithmetic: "split-bf16" (default: the convolutions multiply f32 operands as bf16 hi + lo pairs on the bf16 matrix
         pipe, f32 accumulation; tensors, loss, gradients and Adam are fp32) or "f32" (exact f32 MFMA, about half the speed).
         deterministic: every reduction of the step in a fixed order instead of float atomics -- two runs give the same bits."""
@@ -280,14 +294,15 @@ class Trainer:
         backward pass is queued without waiting, the gradient reduction follows it group by group, then Adam; the loss is
         read last (one synchronisation per step)."""
         heads = [h for h, _ in self.model.heads]
-        key = {"affs_head": ("gt_affs", "affs_weights"), "lsds_head": ("gt_lsds", "lsds_weights")}
+        key = {"affs_head": ("gt_affs", "affs_weights"), "lsds_head": ("gt_lsds", "lsds_weights"),
+               "aff_head": ("gt_affs", "affs_weights"), "lsd_head": ("gt_lsds", "lsds_weights")}   # 2-D heads (unet.HEAD_OF_OUTPUT)
         self.forward_backward(batch["raw"], [batch[key[h][0]] for h in heads], [batch[key[h][1]] for h in heads], wait=False)
         self.optimizer_step()
         return self.read_last_loss()
 
     def predictions(self):
         """{"pred_<x>": float32 CUDA (dims, d, h, w)} of the last step, named like the reference's training_step outputs"""
-        name = {"affs_head": "pred_affs", "lsds_head": "pred_lsds"}
+        name = {"affs_head": "pred_affs", "lsds_head": "pred_lsds", "aff_head": "pred_affs", "lsd_head": "pred_lsds"}
         dev = torch.device("cuda", self.model.device)
         out = {}
         for i, (head, dims) in enumerate(self.model.heads):

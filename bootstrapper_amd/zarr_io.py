@@ -230,6 +230,9 @@ class ZarrArray:
             src = np.ascontiguousarray(np.broadcast_to(np.asarray(src, dtype=self.dtype), shape))
         if src.size == 0:
             return
+        if len(self.shape) > 4:   # the library's chunk copies have four axes (a stacked 2-D snapshot has five)
+            self._setitem_python(box, src)
+            return
         arr, grid, cs, paths = self._copies(box, src, True)
         for d in {os.path.dirname(p) for p in paths}:
             os.makedirs(d, exist_ok=True)
@@ -245,6 +248,16 @@ class ZarrArray:
             inner, outer, _ = self._overlap(box, cidx)
             out[outer] = chunk[inner]
         return out
+
+    def _setitem_python(self, box, src):
+        grid = self._chunk_grid(box)
+        chunks = []
+        for cidx in grid:
+            inner, outer, covers = self._overlap(box, cidx)
+            chunk = np.full(self.chunks, self.fill_value, dtype=self.dtype) if covers else self._read_chunks([cidx])[0].copy()
+            chunk[inner] = src[outer]
+            chunks.append(chunk)
+        self._write_chunks(grid, chunks)
 
     def __getitem__(self, key):
         box = self._norm(key)

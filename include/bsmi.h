@@ -187,6 +187,38 @@ int bsmi_train_lsd_targets(int device, const int64_t *labels_dev, const uint8_t 
                            const int64_t roi_offset[3], const int64_t roi_shape[3], const float sigma[3],
                            const float voxel_size[3], int downsample, float *lsds_dev, float *weights_dev, void *stream);
 
+/* 2-D local-shape-descriptor training targets of a batch of sections, in one launch (reference models/2d_mtlsd/train.py:
+ * Add2DLSDs(labels, gt_lsds, unlabelled, lsds_mask, sigma=(0, s, s), downsample), gp/add_2d_lsds.py: lsd's LsdExtractor
+ * [EXT] in 2-D on every section; restated in tests/lsd2d_ref.py).  6 channels: mean offset (y, x), variances (y, x), Pearson
+ * yx, size -- each in [0, 1], 0 on background.  Statistics per (sub-grid cell, label), staged in LDS, f32.
+ *   labels_dev   int64 [n_sections][H][W]: label sections grown by the window context (3 sigma; zeros where the volume ends)
+ *   unlabelled_dev  uint8 [n_sections][H][W] or NULL: 1 where the ground truth is known
+ *   roi_offset / roi_shape  the output window inside every section (all multiples of `downsample`)
+ *   sigma, voxel_size  (y, x), world units; the window radius 3 sigma / (voxel_size * downsample) is at most 60
+ *   lsds_dev     float [6][n_sections][h][w];  weights_dev  float [6][n_sections][h][w] or NULL: 1 on labelled, known voxels */
+int bsmi_train_lsd2d_targets(int device, const int64_t *labels_dev, const uint8_t *unlabelled_dev, int n_sections,
+                             const int64_t shape[2], const int64_t roi_offset[2], const int64_t roi_shape[2], const float sigma[2],
+                             const float voxel_size[2], int downsample, float *lsds_dev, float *weights_dev, void *stream);
+
+/* Affinity training targets of the output ROI of label arrays that carry the neighbourhood's context (gp.AddAffinities grows
+ * its labels request by the neighbourhood; BalanceLabels then sees the output ROI only).  n_samples independent arrays:
+ * GrowBoundary and the affinities on each whole array, the mask / balance as bsmi_train_affinity_targets states them,
+ * with the positive fraction counted per sample over its ROI (the reference balances every draw before gp.Stack).
+ *   labels_dev      int64 [n_samples][D][H][W]; overwritten with the grown-boundary labels
+ *   unlabelled_dev  uint8 [n_samples][D][H][W] or NULL
+ *   roi_offset / roi_shape  the output ROI inside every array
+ *   affs_dev / weights_dev  float [n][n_samples][d][h][w] (for sections, D = d = 1: the (C, S, h, w) stack of a batch) */
+int bsmi_train_affinity_targets_roi(int device, int64_t *labels_dev, const uint8_t *unlabelled_dev, int n_samples,
+                                    const int64_t shape[3], const int64_t roi_offset[3], const int64_t roi_shape[3],
+                                    const int32_t *neighborhood, int n, int grow_steps, int only_xy, float clip_min,
+                                    float clip_max, float *affs_dev, float *weights_dev, void *stream);
+
+/* Summed-area table of a stack of mask sections: sat_dev uint32 [n_sections][height + 1][width + 1],
+ * sat[s][y][x] = number of non-zero mask voxels of section s above row y and left of column x.  The 2-D sample source
+ * counts the known voxels of an output window with four lookups. */
+int bsmi_train_mask_sat(int device, const uint8_t *mask_dev, int n_sections, int height, int width, uint32_t *sat_dev,
+                        void *stream);
+
 /* Number of CUs the stream bsmi_unet_forward is called on may use (a multiple of 8; -1 restores the
  * default = all CUs of the device, 0 disables the persistent launches).  The big-tile conv layers run
  * as that many persistent workgroups (conv_igemm.hip); set it when the stream carries a CU mask. */

@@ -36,6 +36,18 @@ class UNetConfig(C.Structure):
     ]
 
 
+class StepInfo(C.Structure):
+    """bsmi_unet_step_info of include/bsmi.h"""
+    _fields_ = [("type", C.c_int32), ("materialised", C.c_int32), ("shape", C.c_int32 * 4), ("conv_index", C.c_int32),
+                ("form", C.c_int32), ("flags", C.c_int32), ("bn", C.c_int32), ("ksteps", C.c_int32), ("head", C.c_int32),
+                ("factor", C.c_int32 * 3), ("offset", C.c_int32 * 3), ("prefix", C.c_char * 64)]
+
+
+STEP_TYPES = ("input", "conv", "pool", "up", "head")
+CONV_FORMS = ("gather", "raster-halo", "box-halo", "halo-resident", "first-pass", "winograd F(2x2)", "winograd F(4x4)")
+STEP_FLAGS = {1: "fused-up", 2: "res-low", 4: "split-k"}
+
+
 class Codec(C.Structure):
     """bsmi_codec of include/bsmi_io.h"""
     _fields_ = [("id", C.c_int32), ("level", C.c_int32), ("cname", C.c_int32), ("shuffle", C.c_int32),
@@ -78,6 +90,7 @@ def _load():
         "bsmi_unet_flops": (i32, [p, i64p, C.POINTER(C.c_double)]),
         "bsmi_unet_forward": (i32, [p, i32, vp, i32, i64p, C.POINTER(vp), C.POINTER(vp), vp]),
         "bsmi_unet_debug_activation": (i32, [p, i32, i32, i64p, vp, C.c_uint64]),
+        "bsmi_unet_debug_step_info": (i32, [p, i32, C.POINTER(StepInfo), C.POINTER(i32)]),
         "bsmi_unet_profile_enable": (i32, [p, i32]),
         "bsmi_unet_profile_read": (i32, [p, i32, C.POINTER(i32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double)]),

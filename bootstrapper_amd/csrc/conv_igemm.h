@@ -76,5 +76,8 @@ inline size_t stream_k_ws_bytes(int sk_grid) { return (size_t)sk_grid * kStreamK
 // count); with them, big-tile launches whose tile count is not a multiple of the grid run persistently.
 int launch_conv_igemm(const ConvArgs& a, int precision, TileCfg cfg, hipStream_t stream, float* sk_ws = nullptr,
                       int sk_grid = 0);
+// whether that launch takes the persistent split-K form by the launcher's rule (a kernel body that the compiler spilled is the
+// one thing it cannot tell without the device)
+bool conv_igemm_split_k(const ConvArgs& a, int precision, TileCfg cfg, int sk_grid);
 
 }  // namespace bsmi

@@ -1244,6 +1244,34 @@ TileCfg choose_tile(int cout) {
   return best;
 }
 
+// The launcher's rule for the persistent form with a split-K tail (launch_one below; conv_igemm_split_k reports it): when whole
+// rounds would leave a large share of the last one idle (a batched launch is long: any round count).  Returns the persistent
+// grid, 0 for the plain launch
+static int split_k_grid(bool fused, int BM, int BN, int smem, int ntiles, int nbatch, int sk_grid) {
+  const bool big_tile = BN >= 256;
+  // the fused 64-column tile: two workgroups per CU (80 KB of staging each).  The 2 565 tiles of the 360 -> 60 channel layer are
+  // 5.01 rounds of 512, and the five tiles of the sixth had a tenth of the launch to themselves: 2.62 -> 2.51 ms in the
+  // persistent form; with a last round that is more than half full the plain launch is as fast or faster (60 -> 60: 0.54 / 0.57)
+  static const bool sk64 = [] { const char* e = getenv("BSMI_X3_SK64"); return !(e && e[0] == '0'); }();
+  const bool two_per_cu = fused && BN == 64 && 2 * smem <= 160 * 1024 && sk64;  // (smem: with a dev pad, one per CU)
+  const int grid_sk = two_per_cu ? 2 * sk_grid : sk_grid;
+  const int rounds = ceil_div(ntiles, grid_sk > 0 ? grid_sk : 1);
+  const bool thin_tail = grid_sk > 0 && 2 * (ntiles % grid_sk) < grid_sk;
+  const bool on = sk_grid >= 8 && (big_tile || (two_per_cu && rounds >= 2 && rounds <= 8 && thin_tail)) && ntiles % grid_sk != 0 && (rounds <= 16 || nbatch > 1) &&
+                  (size_t)BM * BN * (two_per_cu ? 2 : 1) <= kStreamKTileElems;
+  return on ? grid_sk : 0;
+}
+
+bool conv_igemm_split_k(const ConvArgs& a, int precision, TileCfg cfg, int sk_grid) {
+  const int BM = 256, BN = tile_bn(cfg);
+  const bool fused = precision == BSMI_PREC_BF16X3 && a.w_lo;
+  if (BN <= 0 || sk_grid < 8) return false;
+  if (BN == 256 && !fused && !two_waves_per_simd()) return false;  // the four-wave 256 x 256 tile has no persistent form
+  const int nbatch = a.nbatch > 1 ? a.nbatch : 1;
+  const int ntiles = ceil_div(a.M, BM) * (a.Npad / BN) * nbatch;
+  return split_k_grid(fused, BM, BN, 4 * (BM + BN) * kStepRowBytes, ntiles, nbatch, sk_grid) != 0;
+}
+
 template <typename T, int BM, int BN, int WM, int WN, int MS = 32, int CUT = 0>
 static int launch_one(const ConvArgs& a, hipStream_t stream, float* sk_ws, int sk_grid) {
   constexpr int smem_need = 4 * (BM + BN) * kStepRowBytes;
@@ -1279,20 +1307,10 @@ static int launch_one(const ConvArgs& a, hipStream_t stream, float* sk_ws, int s
   const int nbatch = a.nbatch > 1 ? a.nbatch : 1;
   if ((nbatch > 1 || a.raw) && !IsFused<T>::value) BSMI_FAIL(BSMI_ERR_INVALID, "batched / raw-sum conv launches exist in the fused split-bf16 kernels only");
   const int ntiles = ceil_div(a.M, BM) * (a.Npad / BN) * nbatch;
-  // persistent + split-K tail when whole rounds would leave a large share of the last one idle (a batched launch is long: any round count)
-  const bool big_tile = BN >= 256;
-  // the fused 64-column tile: two workgroups per CU (80 KB of staging each).  The 2 565 tiles of the 360 -> 60 channel layer are
-  // 5.01 rounds of 512, and the five tiles of the sixth had a tenth of the launch to themselves: 2.62 -> 2.51 ms in the
-  // persistent form; with a last round that is more than half full the plain launch is as fast or faster (60 -> 60: 0.54 / 0.57)
-  static const bool sk64 = [] { const char* e = getenv("BSMI_X3_SK64"); return !(e && e[0] == '0'); }();
-  const bool two_per_cu = IsFused<T>::value && BN == 64 && 2 * smem <= 160 * 1024 && sk64;  // (smem: with a dev pad, one per CU)
-  const int grid_sk = two_per_cu ? 2 * sk_grid : sk_grid;
-  const int rounds = ceil_div(ntiles, grid_sk > 0 ? grid_sk : 1);
-  const bool thin_tail = grid_sk > 0 && 2 * (ntiles % grid_sk) < grid_sk;
+  const int grid_sk = split_k_grid(IsFused<T>::value, BM, BN, smem, ntiles, nbatch, sk_grid);
   bool persistent = false;
   if constexpr (has_sk)
-  if (sk_ws && sk_ok && sk_grid >= 8 && (big_tile || (two_per_cu && rounds >= 2 && rounds <= 8 && thin_tail)) && ntiles % grid_sk != 0 && (rounds <= 16 || nbatch > 1) &&
-      (size_t)BM * BN * (two_per_cu ? 2 : 1) <= kStreamKTileElems) {
+  if (sk_ws && sk_ok && grid_sk) {
     int* counters = (int*)(sk_ws + (size_t)sk_grid * kStreamKTileElems);
     const int sk_grid_arg = grid_sk;
     hipLaunchKernelGGL(kern_sk, dim3(sk_grid_arg), dim3(64 * WM * WN), smem, stream, a, sk_ws, counters);

@@ -50,6 +50,8 @@ int rh_halo_pieces(TileCfg cfg);
 bool rh_supported(TileCfg cfg, int Win, int ky, int kx);
 
 int launch_conv_rh(const RhArgs& a, int precision, TileCfg cfg, hipStream_t stream, float* sk_ws = nullptr, int sk_grid = 0);
+// whether that launch takes the persistent split-K form by the launcher's rule
+bool conv_rh_split_k(const RhArgs& a, TileCfg cfg, int sk_grid);
 
 // (A fused split-bf16 form of this kernel, conv_rh_x3_kernel -- 32 x 64 wave tiles, one barrier per K-step of 24 MFMAs -- existed in
 // rounds 2 and 3 as an opt-in and lost to the gather kernel; conv_h16.hip is the halo form of the split mode.)

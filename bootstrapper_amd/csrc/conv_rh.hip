@@ -497,6 +497,14 @@ static int launch_rh_cfg(const RhArgs& a, TileCfg cfg, hipStream_t stream, float
   }
 }
 
+// launch_rh_one's rule for its persistent split-K form, for bsmi_unet_debug_step_info (only the 256-column tile has that form)
+bool conv_rh_split_k(const RhArgs& a, TileCfg cfg, int sk_grid) {
+  const int BN = tile_bn(cfg);
+  if (!(BN >= 256 && BN < 320) || sk_grid < 8) return false;
+  const int ntiles = ceil_div(a.Q, 256) * (a.Npad / BN);
+  return ntiles % sk_grid != 0 && ceil_div(ntiles, sk_grid) <= 16 && (size_t)256 * BN <= kStreamKTileElems;
+}
+
 int launch_conv_rh(const RhArgs& a, int precision, TileCfg cfg, hipStream_t stream, float* sk_ws, int sk_grid) {
   if (a.Q <= 0 || a.nsteps <= 0 || a.nphases <= 0 || a.Npad % tile_bn(cfg) != 0)
     BSMI_FAIL(BSMI_ERR_INVALID, "raster-halo conv launch: bad geometry Q=%d nsteps=%d Npad=%d", a.Q, a.nsteps, a.Npad);

@@ -243,6 +243,30 @@ class Model:
         check(lib.bsmi_unet_debug_activation(self._h, int(step), int(what), shape, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
+    def plan_steps(self):
+        """The launches of the last forward's plan, in order, as dicts: type (input / conv / pool / up / head), whether the
+        forward materialised the step's output (debug_activation refuses the others), shape (D, H, W, C); conv steps also
+        carry the state-dict prefix of their ConvPass, the conv index inside it, the kernel form that ran, its flags
+        (fused-up, res-low, split-k), the GEMM tile's BN and the K-step count."""
+        n = C.c_int()
+        check(lib.bsmi_unet_debug_step_info(self._h, 0, None, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            si = _lib.StepInfo()
+            check(lib.bsmi_unet_debug_step_info(self._h, i, C.byref(si), None))
+            d = {"step": i, "type": _lib.STEP_TYPES[si.type], "materialised": bool(si.materialised), "shape": tuple(si.shape)}
+            if d["type"] == "conv":
+                d.update(prefix=si.prefix.decode(), conv=si.conv_index, form=_lib.CONV_FORMS[si.form],
+                         flags=tuple(name for bit, name in _lib.STEP_FLAGS.items() if si.flags & bit), bn=si.bn, ksteps=si.ksteps)
+            elif d["type"] == "head":
+                d.update(prefix=si.prefix.decode(), head=si.head)
+            elif d["type"] in ("pool", "up"):
+                d.update(factor=tuple(si.factor))
+                if d["type"] == "up":
+                    d.update(offset=tuple(si.offset))
+            out.append(d)
+        return out
+
     # -- forward -----------------------------------------------------------------------
     def _run(self, raw, raw_dtype, in_shape, want_f32, want_u8):
         dev = torch.device("cuda", self.device)

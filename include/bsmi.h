@@ -259,9 +259,47 @@ int bsmi_debug_check_guards(void);
 /* Development aid: the output tensor of launch `step` of the last forward (launch order as in
  * bsmi_unet_profile_read), as float32 channels-last [D][H][W][C] on the host, whatever the precision mode stores
  * (f32, bf16, or the hi + lo planes of the split mode).  shape_out = {D, H, W, C}; host_out may be NULL to query
- * the shape.  what: 0 = the value, 1 / 2 = only the hi / lo plane of the split mode.  Synchronises the device. */
+ * the shape.  what: 0 = the value, 1 / 2 = only the hi / lo plane of the split mode.  Synchronises the device.
+ * A step that the last forward did not materialise -- input preparation and the first convolution when the first ConvPass
+ * ran as one launch, an upsampling step that was fused into its Winograd consumers -- fails with BSMI_ERR_STATE. */
 int bsmi_unet_debug_activation(bsmi_unet *h, int step, int what, int64_t shape_out[4], float *host_out,
                                uint64_t capacity);
+
+/* What launch `step` of the last forward's plan is (what BSMI_PLAN_DEBUG prints, as data). */
+enum { BSMI_STEP_INPUT = 0, BSMI_STEP_CONV = 1, BSMI_STEP_POOL = 2, BSMI_STEP_UP = 3, BSMI_STEP_HEAD = 4 };
+/* kernel form of a conv step */
+enum {
+  BSMI_FORM_GATHER = 0,        /* implicit GEMM, rows gathered per K-step (conv_igemm) */
+  BSMI_FORM_RASTER_HALO = 1,   /* conv_rh */
+  BSMI_FORM_BOX_HALO = 2,      /* conv_box */
+  BSMI_FORM_HALO_RESIDENT = 3, /* conv_h16 */
+  BSMI_FORM_FIRST_PASS = 4,    /* the whole first ConvPass as one launch (first_pass) */
+  BSMI_FORM_WINO2 = 5,         /* Winograd F(2x2, 3x3) around the batched GEMM */
+  BSMI_FORM_WINO4 = 6,         /* Winograd F(4x4, 3x3) */
+  BSMI_FORM_COUNT = 7
+};
+/* flags of a conv step */
+enum {
+  BSMI_STEP_FUSED_UP = 1,      /* a source is read through an on-the-fly upsampling (the UP step before it is not materialised) */
+  BSMI_STEP_RES_LOW = 2,       /* part of the residual branch runs as a GEMM of its own below the upsampling */
+  BSMI_STEP_SPLIT_K = 4        /* the launcher's rule sends (one of) the GEMM launches of this step to the persistent split-K form */
+};
+typedef struct {
+  int32_t type;          /* BSMI_STEP_* */
+  int32_t materialised;  /* 0: the forward writes no tensor for this step; bsmi_unet_debug_activation refuses it */
+  int32_t shape[4];      /* D, H, W, C of the step's output (head: of its input) */
+  int32_t conv_index;    /* conv steps: index inside the ConvPass */
+  int32_t form;          /* conv steps: BSMI_FORM_* */
+  int32_t flags;         /* conv steps: BSMI_STEP_FUSED_UP | ... */
+  int32_t bn;            /* conv steps: columns of the GEMM tile (0: the form has no such tile) */
+  int32_t ksteps;        /* conv steps: K-steps of the (batched) GEMM as the kernel walks them */
+  int32_t head;          /* head steps: index of the head */
+  int32_t factor[3];     /* pool / up steps */
+  int32_t offset[3];     /* up steps: crop origin inside the upsampled map */
+  char prefix[64];       /* conv steps: state-dict prefix of the ConvPass; head steps: of the head */
+} bsmi_unet_step_info;
+/* *n_steps (optional) receives the number of steps; info may be NULL to query it alone. */
+int bsmi_unet_debug_step_info(bsmi_unet *h, int step, bsmi_unet_step_info *info, int *n_steps);
 
 /* Reflect-padded block extraction (gp.Pad(raw, None, mode="reflect") +
  * ArraySource ROI read, models/3d_affs/predict.py:145-148): copies the window

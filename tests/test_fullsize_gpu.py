@@ -172,7 +172,9 @@ def test_full_net_volume_pipeline_vs_cpu_blockwise():
     assert torch.equal(segs2, segs)
 
 
-@pytest.mark.parametrize("variant,env", [
+# the conv kernel variants that layer sizes or environment variables (read once per process) select; tests/test_layers_gpu.py
+# runs its per-launch cases under the same list
+CONV_KERNEL_VARIANTS = [
     ("raster-halo kernel", {"BSMI_USE_RH": "1"}),
     ("raster-halo kernel, persistent split-K tail", {"BSMI_USE_RH": "1", "BSMI_SK_GRID": "8", "BSMI_TILE_EFF": "0.01,0.01,0.01,1,0.01"}),
     ("persistent split-K tail, 256x256 tiles", {"BSMI_SK_GRID": "8", "BSMI_TILE_EFF": "0.01,0.01,0.01,1,0.01"}),
@@ -200,7 +202,10 @@ def test_full_net_volume_pipeline_vs_cpu_blockwise():
     ("halo-resident form (conv_h16.hip) on every stage of at most 64 output channels", {"BSMI_H16": "2"}),
     ("halo-resident form on every such stage, the first ConvPass included", {"BSMI_H16": "2", "BSMI_FUSED_FIRST": "0", "BSMI_WINO": "0"}),
     ("no halo-resident stage", {"BSMI_H16": "0"}),
-])
+]
+
+
+@pytest.mark.parametrize("variant,env", CONV_KERNEL_VARIANTS)
 def test_conv_kernel_variants_in_subprocess(variant, env):
     """The conv kernel variants that the golden nets do not reach by themselves (they are chosen by layer
     size, or opt-in) are selected through environment variables read once per process: run the whole U-Net

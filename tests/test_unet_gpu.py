@@ -72,11 +72,10 @@ def test_u8_pipeline_matches_oracle(golden_dir, tag):
     assert (diff == 0).mean() > 0.99
 
 
-def test_random_shapes_against_oracle():
-    """Seeded random weights, non-golden shapes (ragged: W != H, odd depth), mixed kernel
-    sizes (1,3,3)/(3,3,3) as the 3d_affs_from_* configs use; oracle = torch CPU fp32."""
-    from bootstrapper_amd.unet import Model
-    from oracle import unet_ref as R
+def random_ragged_nets():
+    """Seeded random weights, non-golden shapes (ragged: W != H, odd depth), mixed kernel sizes (1,3,3)/(3,3,3) as the
+    3d_affs_from_* configs use, factor 3, (2,2,2) pooling, single-conv passes: yields (case, oracle cfg, state dict, raw u8).
+    (also the nets of case B of tests/test_layers_gpu.py)"""
     rng = np.random.default_rng(11)
     cfgs = [
         dict(num_fmaps=5, inc=3, ksd=[[[3, 3, 3], [3, 3, 3]]] * 3, ksu=[[[3, 3, 3], [3, 3, 3]]] * 2,
@@ -108,6 +107,15 @@ def test_random_shapes_against_oracle():
         cfg = dict(in_channels=1, num_fmaps=c["num_fmaps"], fmap_inc_factor=c["inc"],
                    downsample_factors=c["dfs"], kernel_size_down=c["ksd"], kernel_size_up=c["ksu"])
         raw = rng.integers(0, 256, size=c["shape"], dtype=np.uint8)
+        yield c, cfg, sd, raw
+
+
+def test_random_shapes_against_oracle():
+    """Seeded random weights, non-golden shapes (ragged: W != H, odd depth), mixed kernel
+    sizes (1,3,3)/(3,3,3) as the 3d_affs_from_* configs use; oracle = torch CPU fp32."""
+    from bootstrapper_amd.unet import Model
+    from oracle import unet_ref as R
+    for c, cfg, sd, raw in random_ragged_nets():
         ref = R.predict_block(cfg, sd, raw, ["affs_head"])[0]
         nc = dict(cfg, outputs={"3d_affs": {"dims": 6}})
         m = Model(nc, precision="f32").load_state_dict(sd)

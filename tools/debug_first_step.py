@@ -24,7 +24,7 @@ def dump(m):
             acts.append(m.debug_activation(step))
         except Exception as e:
             if "out of range" in str(e): break
-            acts.append(None)  # a head step: writes the caller's buffers
+            acts.append(None)  # a head step (writes the caller's buffers) or a step that is not materialised
         step += 1
     return acts
 
@@ -58,7 +58,7 @@ with torch.cuda.stream(sv):
         print(f"--- corrupted prediction {found}: {int((u != ref).sum())} u8 values differ", flush=True)
         first = True
         for i, (a, b) in enumerate(zip(clean, dirty)):
-            if a is None: print(f"  launch {i:2d}: head"); continue
+            if a is None: print(f"  launch {i:2d}: head / not materialised"); continue
             ne = ~np.isclose(a, b, rtol=0, atol=0, equal_nan=True)
             n = int(ne.sum())
             line = f"  launch {i:2d}: shape {a.shape}: {n} of {a.size} values differ"

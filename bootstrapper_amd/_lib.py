@@ -63,6 +63,7 @@ class ChunkCopy(C.Structure):
 CODEC_RAW, CODEC_ZLIB, CODEC_GZIP, CODEC_ZSTD, CODEC_LZ4, CODEC_BLOSC = range(6)
 BLOSC_LZ4, BLOSC_ZLIB, BLOSC_ZSTD = 1, 3, 4
 CHUNK_MISSING = 1
+MORPH_DILATE, MORPH_ERODE = 0, 1
 
 
 class BsmiError(RuntimeError):
@@ -159,6 +160,9 @@ def _load():
         "bsmi_eval_pairs_u64": (i32, [p, vp, vp, vp, i64p, i32, vp]),
         "bsmi_eval_pairs_read": (i32, [p, vp, vp, vp, C.c_uint64, vp, vp]),
         "bsmi_eval_status": (i32, [p, vp]),
+        "bsmi_label_morph_u64": (i32, [i32, vp, i64p, i32, i32, i32, vp, vp, vp]),
+        "bsmi_label_fill_holes_scratch_bytes": (C.c_size_t, [i64p, C.c_uint64]),
+        "bsmi_label_fill_holes_u64": (i32, [i32, vp, i64p, i32, vp, vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

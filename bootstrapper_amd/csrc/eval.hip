@@ -19,6 +19,7 @@
 
 #include "../../include/bsmi.h"
 #include "common.h"
+#include "u64_table.h"
 
 #include "dev_guard.h"  // last: routes hipMalloc / hipFree through the guarded allocator (BSMI_GUARD_MB)
 
@@ -42,7 +43,6 @@ struct bsmi_eval {
 namespace bsmi {
 namespace {
 
-constexpr uint64_t kEmpty = ~0ull;
 constexpr int kMaxOffsets = 16;
 constexpr int kRowsPerBlock = 16;
 
@@ -154,16 +154,7 @@ __global__ void __launch_bounds__(256) aff_norm_kernel(AffArgs a) {
     if (hist[i]) atomicAdd(&a.hist[i], (unsigned long long)hist[i]);
 }
 
-// ---- contingency table ----
-
-__device__ __forceinline__ uint64_t mix64(uint64_t k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return k;
-}
+// ---- contingency table (mix64, table_slot: u64_table.h) ----
 
 struct PairArgs {
   const uint64_t* gt;
@@ -177,28 +168,6 @@ struct PairArgs {
   unsigned long long* pair_counts;
   uint32_t* flags;
 };
-
-// slot of `key` in an open-addressing table of cap (power of two) slots, inserted if absent; -1 (and an overflow bit) when
-// the table is full.  `key` must not be kEmpty.
-__device__ int64_t table_slot(uint64_t* keys, uint64_t cap, uint64_t key, uint32_t* inserts, uint32_t* flags, uint32_t bit) {
-  uint64_t h = mix64(key) & (cap - 1);
-  for (uint64_t probe = 0; probe < cap; ++probe) {
-    uint64_t k = __atomic_load_n(&keys[h], __ATOMIC_RELAXED);
-    if (k == key) return (int64_t)h;
-    if (k == kEmpty) {
-      const unsigned long long old = atomicCAS((unsigned long long*)&keys[h], (unsigned long long)kEmpty, (unsigned long long)key);
-      if (old == kEmpty) {
-        // a table past 7/8 full probes long: report it as an overflow before it fills up
-        if (atomicAdd(inserts, 1u) + 1 > (uint32_t)(cap - cap / 8)) atomicOr(flags, bit);
-        return (int64_t)h;
-      }
-      if (old == key) return (int64_t)h;
-    }
-    h = (h + 1) & (cap - 1);
-  }
-  atomicOr(flags, bit);
-  return -1;
-}
 
 // an id's dense index: its slot; the id 2^64-1 (the empty marker) has the extra slot `cap`, whose key reads as itself
 __device__ __forceinline__ int64_t id_slot(uint64_t* keys, uint64_t cap, uint64_t id, uint32_t* inserts, uint32_t* flags) {

@@ -288,6 +288,48 @@ def lut_relabel(labels, keys, vals, out=None):
     return out
 
 
+def label_morph(labels, op, iterations=1, xy=False, out=None, tmp=None):
+    """`iterations` steps of dilate (_lib.MORPH_DILATE) or erode (_lib.MORPH_ERODE) on an int64 CUDA tensor [D][H][W] of uint64
+    ids (include/bsmi.h bsmi_label_morph_u64: the rule, written out); xy: every z section on its own.  `out` / `tmp`: buffers
+    to use (tmp: the ping-pong buffer of two or more iterations), neither may be `labels`.  Asynchronous on the current stream."""
+    if labels.dtype != torch.int64 or not labels.is_cuda or labels.dim() != 3 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 CUDA tensor of shape (D, H, W)")
+    out = torch.empty_like(labels) if out is None else out
+    if tmp is None and iterations > 1:
+        tmp = torch.empty_like(labels)
+    for t in (out, tmp):
+        if t is not None and (t.dtype != torch.int64 or t.device != labels.device or t.numel() < labels.numel() or not t.is_contiguous()):
+            raise ValueError("out / tmp must be contiguous int64 tensors of the volume's size on its device")
+    stream = C.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+    check(lib.bsmi_label_morph_u64(labels.device.index, C.c_void_p(labels.data_ptr()), _lib.i64x3(labels.shape), int(op), int(iterations),
+                                   1 if xy else 0, C.c_void_p(out.data_ptr()), C.c_void_p(tmp.data_ptr() if tmp is not None else None), stream))
+    return out
+
+
+def label_fill_holes(labels, xy=False, out=None, table_capacity=None):
+    """fill_holes of include/bsmi.h (bsmi_label_fill_holes_u64) on an int64 CUDA tensor [D][H][W] of uint64 ids -> (out, number
+    of components filled).  The face table starts at `table_capacity` slots (default: by the volume's size) and is doubled
+    while the call reports an overflow; a table that cannot grow any further raises.  Synchronises the current stream."""
+    if labels.dtype != torch.int64 or not labels.is_cuda or labels.dim() != 3 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 CUDA tensor of shape (D, H, W)")
+    out = torch.empty_like(labels) if out is None else out
+    shape = _lib.i64x3(labels.shape)
+    cap = int(table_capacity) if table_capacity else max(1 << 16, 1 << max(0, (labels.numel() // 256 - 1).bit_length()))
+    stream = C.c_void_p(torch.cuda.current_stream(labels.device).cuda_stream)
+    filled = C.c_uint64(0)
+    while True:
+        nbytes = int(lib.bsmi_label_fill_holes_scratch_bytes(shape, cap))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=labels.device)
+        rc = lib.bsmi_label_fill_holes_u64(labels.device.index, C.c_void_p(labels.data_ptr()), shape, 1 if xy else 0, C.c_void_p(out.data_ptr()),
+                                           C.c_void_p(scratch.data_ptr()), nbytes, cap, C.byref(filled), stream)
+        if rc == _lib.ERR_OVERFLOW and cap < (1 << 31):
+            del scratch
+            cap *= 2
+            continue
+        check(rc)
+        return out, int(filled.value)
+
+
 def lut_relabel_multi(labels, keys, vals, out=None):
     """lut_relabel for several value columns at once -- one segmentation per threshold out of one fragment volume: vals int64
     [T][m] (CUDA or host), -> out int64 [T] + labels.shape.  One look-up per run of equal ids serves every column."""

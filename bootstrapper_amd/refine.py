@@ -1,8 +1,9 @@
-"""`bs refine` statistics filters and id remap on the device.
+"""`bs refine` statistics filters, id remap and label-preserving morphology on the device.
 
 Same commands, options, statistics and default output names as /root/reference/bootstrapper/refine.py (`size_filter`
-:176-213, `outlier_filter` :131-168, `z_filter` :221-257, `remap` :272-307; `morph` needs fastmorph [EXT] and is not part
-of this engine).  Structure: the label volume is scanned once on the device into an `ObjectTable` (ids, voxel counts,
+:176-213, `outlier_filter` :131-168, `z_filter` :221-257, `remap` :272-307, `morph` :310-401).  `morph` follows the
+reference's block grid and seams; what one operation does to the array it sees is this project's own rule (fastmorph [EXT] is
+absent: DESIGN.md section 7g, restated in tests/morph_ref.py, parity unpinned).  Structure of the filters: the label volume is scanned once on the device into an `ObjectTable` (ids, voxel counts,
 first / last section: `bsmi_label_table_u64` tile by tile), a filter is a rule that turns the table into a rejection
 mask (`FILTERS`), and `run_filter` writes the volume with the rejected ids zeroed through `bsmi_lut_relabel`.
 """
@@ -234,9 +235,137 @@ def remap(in_array, out_array=None, remove_ids=None, merge_ids=(), device=0):
     return target
 
 
+MORPH_OPS = ("dilate", "erode", "opening", "closing", "fill_holes")
+# fill_holes merges an enclosed component into its dominant neighbour when that neighbour holds at least 19 / 20 of the
+# component's faces (fastmorph's merge_threshold=0.95, reference refine.py:323, compared in integers; BSMI_MORPH_MERGE_NUM / _DEN)
+MERGE_THRESHOLD = (19, 20)
+WRITES_IN_FLIGHT = 2   # block rows queued for writing before the next one waits
+
+
+def morph_blocks(shape, chunks, block_size, context, xy):
+    """The reference's block grid (refine.py:47-72, `_morph_block` :347-360) as a list of (write, read) boxes, each a tuple of
+    (start, stop) per axis: write blocks of one chunk along z and `block_size` snapped to whole chunks along y and x, from the
+    volume's first voxel, the last of an axis shrunk to the volume; the read block is the write block grown by the halo
+    ((0, context, context) with xy, else context on every axis) and clipped to the volume."""
+    cz, cy, cx = (int(c) for c in chunks)
+    block = (cz, cy * max(1, round(block_size / cy)), cx * max(1, round(block_size / cx)))
+    halo = (0, context, context) if xy else (context,) * 3
+    starts = [range(0, int(n), b) for n, b in zip(shape, block)]
+    out = []
+    for z in starts[0]:
+        for y in starts[1]:
+            for x in starts[2]:
+                write = tuple((o, min(o + b, int(n))) for o, b, n in zip((z, y, x), block, shape))
+                read = tuple((max(0, lo - h), min(int(n), hi + h)) for (lo, hi), h, n in zip(write, halo, shape))
+                out.append((write, read))
+    return out
+
+
+def apply_morph(labels, op, iterations=1, xy=False):
+    """one operation of MORPH_OPS on an int64 CUDA tensor [D][H][W] of uint64 ids (the array the operation sees; with xy every
+    z section on its own) -> a new tensor; `labels` is used as work space by opening / closing and does not survive them"""
+    from . import _lib
+    from .post.engine import label_fill_holes, label_morph
+    if op == "fill_holes":   # `iterations` does not apply (refine.py:342-343)
+        return label_fill_holes(labels, xy)[0]
+    if op in ("dilate", "erode"):
+        return label_morph(labels, _lib.MORPH_DILATE if op == "dilate" else _lib.MORPH_ERODE, iterations, xy)
+    if op not in ("opening", "closing"):
+        raise ValueError(op)
+    first, second = (_lib.MORPH_ERODE, _lib.MORPH_DILATE) if op == "opening" else (_lib.MORPH_DILATE, _lib.MORPH_ERODE)
+    a, b = labels.new_empty(labels.shape), labels.new_empty(labels.shape)
+    label_morph(labels, first, iterations, xy, out=a, tmp=b if iterations > 1 else None)
+    return label_morph(a, second, iterations, xy, out=b, tmp=labels if iterations > 1 else None)
+
+
+def _morph_bytes(read_voxels, row_voxels, op, iterations):
+    """device memory one block needs: the read block, the result, the ping-pong buffer (a third volume for opening / closing,
+    none for one dilate / erode step), fill_holes' work space (parents, flags, tables), the block rows queued for writing"""
+    volumes = 2 + (1 if op in ("opening", "closing") or (op in ("dilate", "erode") and iterations > 1) else 0)
+    extra = read_voxels * 5 + 3 * 8 * max(1 << 16, read_voxels // 128) if op == "fill_holes" else 0
+    return read_voxels * 8 * volumes + extra + (WRITES_IN_FLIGHT + 1) * row_voxels * 8
+
+
+def morph(in_array, out_array=None, op=None, iterations=1, xy=False, context=64, block_size=2048, num_workers=20, device=0):
+    """Apply a morphological operation to a labelled volume, blockwise (refine.py:363-401).
+
+    Operations are label-preserving (multilabel). With --xy the operation runs on each z-section independently, otherwise in
+    3D over the block. The halo (--context) supplies neighbouring data so labels stay consistent across block seams; it is
+    clipped at the true volume edge.  `num_workers` is accepted for the reference's command line and unused: one device
+    works through the blocks."""
+    import collections
+    import torch
+    if op not in MORPH_OPS:
+        raise click.ClickException(f"--op must be one of {', '.join(MORPH_OPS)}")
+    if not 1 <= iterations <= 255:
+        raise click.ClickException("--iterations must be in 1..255")
+    if context < 0 or block_size < 1:
+        raise click.ClickException("--context must be >= 0 and --block_size >= 1")
+    in_ds = open_ds(in_array)
+    if len(in_ds.shape) != 3 or in_ds.dtype.kind not in "iu":
+        raise click.ClickException(f"{in_array}: morph takes a 3-D dataset of integer labels, not {in_ds.shape} {in_ds.dtype}")
+    target = out_array or derived_dataset(in_array, op)
+    print(f"Writing to {target}")
+    blocks = morph_blocks(in_ds.shape, in_ds.chunks, block_size, context, xy)
+    dev = torch.device("cuda", device)
+    nx = int(in_ds.shape[2])
+    extent = lambda box: tuple(hi - lo for lo, hi in box)  # noqa: E731
+    most = max((int(np.prod(extent(r))) for _, r in blocks), default=0)
+    row = max((extent(w)[0] * extent(w)[1] * nx for w, _ in blocks), default=0)
+    # free = what the driver reports plus what this process's allocator holds without using it
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)
+    need = _morph_bytes(most, row, op, iterations)
+    if need > free:
+        raise click.ClickException(f"a block of {most} voxels with its buffers needs {need / 2**30:.1f} GiB of device memory, "
+                                   f"{free / 2**30:.1f} GiB are free: lower --block_size (or --context)")
+    out_ds = _empty_copy(in_ds, target)
+    as_u64 = in_ds.dtype == np.uint64
+    writer = None
+    if as_u64:
+        from .post.watershed import _LayerWriter
+        writer = _LayerWriter(dev, int(in_ds.chunks[0]))
+    queued = collections.deque()   # (row buffer, its write futures), oldest first
+    spare = []
+    try:
+        with torch.cuda.device(dev):
+            rowbuf = None
+            for write, read in blocks:
+                data = in_ds[tuple(slice(lo, hi) for lo, hi in read)]
+                lab = torch.from_numpy(np.ascontiguousarray(data).astype(np.uint64, copy=False).view(np.int64)).to(dev)
+                res = apply_morph(lab, op, iterations, xy)
+                cut = res[tuple(slice(w[0] - r[0], w[1] - r[0]) for w, r in zip(write, read))]
+                if not as_u64:
+                    out_ds[tuple(slice(lo, hi) for lo, hi in write)] = cut.cpu().numpy().view(np.uint64).astype(in_ds.dtype)
+                    continue
+                # whole rows of x go to the dataset writer: the blocks of a row are gathered in one buffer on the device
+                (z0, z1), (y0, y1), (x0, x1) = write
+                if x0 == 0:
+                    while len(queued) >= WRITES_IN_FLIGHT:   # bounded write-behind: wait for the oldest row before the next
+                        buf, futures = queued.popleft()
+                        for f in futures:
+                            f.result()
+                        writer.futures = writer.futures[len(futures):]
+                        spare.append(buf)
+                    want = (z1 - z0) * (y1 - y0) * nx
+                    fits = next((i for i, b in enumerate(spare) if b.numel() >= want), None)
+                    flat = torch.empty(want, dtype=torch.int64, device=dev) if fits is None else spare.pop(fits)
+                    rowbuf = flat[:want].view(z1 - z0, y1 - y0, nx)
+                rowbuf[:, :, x0:x1].copy_(cut)
+                if x1 == nx:
+                    before = len(writer.futures)
+                    writer.submit(out_ds, rowbuf, z0, y0)
+                    queued.append((rowbuf.view(-1), writer.futures[before:]))
+            if writer is not None:
+                writer.drain()
+    finally:
+        if writer is not None:
+            writer.close()
+    return target
+
+
 @click.group()
 def refine():
-    """Refine segmented volumes: size/outlier/z filtering, id remap."""
+    """Refine segmented volumes: size/outlier/z filtering, id remap, morphology."""
 
 
 def _cmd(name, fn, options):
@@ -253,3 +382,13 @@ _cmd("size_filter", size_filter, _io + [click.option("--min_size", type=int, def
 _cmd("outlier_filter", outlier_filter, _io + [click.option("--num_std", "-n", type=float, default=3.0), click.option("--min_size", type=int, default=0), _dry])
 _cmd("z_filter", z_filter, _io + [click.option("--min_z", "-z", type=int, default=1), _dry])
 _cmd("remap", remap, _io + [click.option("--remove_ids", "-r", type=str, default=None), click.option("--merge_ids", "-m", type=str, multiple=True)])
+_cmd("morph", morph, _io + [
+    click.option("--op", type=click.Choice(MORPH_OPS), required=True, help="Morphological operation"),
+    click.option("--iterations", "-n", type=int, default=1, help="Iterations for dilate/erode/opening/closing"),
+    click.option("--xy", is_flag=True, default=False, help="Apply per z-section (2D) instead of 3D"),
+    click.option("--context", "-c", type=int, default=64,
+                 help="Halo in voxels covering the op's reach (xy only with --xy, else xy and z); >= iterations for dilate/erode, "
+                      ">= 2*iterations for opening/closing, >= largest hole for fill_holes"),
+    click.option("--block_size", "-b", type=int, default=2048,
+                 help="XY write-block size in voxels (snapped to a chunk multiple; z tiles by the chunk)"),
+    click.option("--num_workers", "-w", type=int, default=20, help="accepted and unused: one device works through the blocks")])

@@ -555,6 +555,43 @@ int bsmi_eval_pairs_read(bsmi_eval *h, uint64_t *gt_out_dev, uint64_t *seg_out_d
  * Synchronises `stream`. */
 int bsmi_eval_status(bsmi_eval *h, void *stream);
 
+/* ---- label-preserving morphology (`bs refine morph`) ----------------------------------------------------------
+ * Replaces fastmorph as the reference calls it (refine.py:310-344 `_apply_morph`; the package is third party and absent:
+ * the rule below is this project's own, restated in tests/morph_ref.py, parity unpinned).
+ * The array A that one operation sees is the whole volume [D][H][W] with a 3 x 3 x 3 stencil, or, with xy != 0, every z
+ * section on its own with a 3 x 3 stencil (all sections in one launch).
+ *   dilate (fastmorph.dilate, background_only=True, refine.py:330-332): a non-zero voxel keeps its id; a zero voxel takes
+ *     the most frequent non-zero id among the stencil voxels inside A, ties to the smallest id, 0 if there is none.
+ *   erode (fastmorph.erode, erode_border=True, refine.py:333-335): a non-zero voxel keeps its id only if every stencil
+ *     voxel holds the same id; positions outside A count as background, so ids on A's faces always go.
+ * `iterations` (1..255) applies the step that many times, each on the previous result; opening and closing
+ * (refine.py:336-341) are two calls.  tmp_dev: ping-pong buffer of the volume's size, may be NULL for one iteration.
+ * in_dev is never written; in_dev, out_dev and tmp_dev must differ (BSMI_ERR_INVALID).  One launch per iteration,
+ * 16 bytes of HBM per voxel each; asynchronous on `stream`. */
+#define BSMI_MORPH_DILATE 0
+#define BSMI_MORPH_ERODE 1
+int bsmi_label_morph_u64(int device, const uint64_t *in_dev, const int64_t shape[3], int op, int iterations, int xy,
+                         uint64_t *out_dev, uint64_t *tmp_dev, void *stream);
+
+/* fill_holes (stands in for fastmorph.fill_holes_v2(fix_borders=two_d, merge_threshold=0.95), refine.py:317-326).
+ * Components are maximal face-connected sets of voxels of A with equal id (6-neighbourhood, 4-neighbourhood with xy != 0),
+ * id 0 included.  A component with a voxel on a face of A (an edge of its section with xy) is left alone.  For every
+ * other component C the faces between a voxel of C and a face-neighbour outside C are counted per neighbouring id; T is
+ * their total, L the non-zero neighbouring id with the largest count n_L (ties to the smallest id); if
+ * BSMI_MORPH_MERGE_DEN * n_L >= BSMI_MORPH_MERGE_NUM * T (0.95 in integers) every voxel of C takes the id L.  All
+ * decisions are taken on the input and applied at once (no chaining).
+ * scratch_dev: bsmi_label_fill_holes_scratch_bytes(shape, table_capacity) bytes on the device; table_capacity: slots
+ * (a power of two in [2, 2^31]) of the (component, neighbouring id) face table and of its id table.  Fewer than 2^32 - 1
+ * voxels per call.  The decision runs on the host from the read-out table, so the call synchronises `stream` and a full
+ * table comes back from the call itself as BSMI_ERR_OVERFLOW (out_dev is then undefined; call again with a larger
+ * table).  *n_filled (optional, host): the number of components that changed id. */
+#define BSMI_MORPH_MERGE_NUM 19ull
+#define BSMI_MORPH_MERGE_DEN 20ull
+size_t bsmi_label_fill_holes_scratch_bytes(const int64_t shape[3], uint64_t table_capacity);
+int bsmi_label_fill_holes_u64(int device, const uint64_t *in_dev, const int64_t shape[3], int xy, uint64_t *out_dev,
+                              void *scratch_dev, size_t scratch_bytes, uint64_t table_capacity, uint64_t *n_filled,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

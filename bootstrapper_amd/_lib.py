@@ -157,6 +157,8 @@ def _load():
         "bsmi_eval_destroy": (i32, [p]),
         "bsmi_eval_aff_errors_u8": (i32, [p, vp, i64p, i64p, vp, i32, i64p, vp, C.POINTER(C.c_int32), i64p, C.c_float, C.c_float,
                                           C.c_int64, vp, vp, vp, vp]),
+        "bsmi_eval_lsd_errors_u8": (i32, [p, vp, i64p, i64p, vp, vp, i64p, i64p, i64p, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          i32, C.c_float, C.c_float, C.c_int64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp]),
         "bsmi_eval_pairs_u64": (i32, [p, vp, vp, vp, i64p, i32, vp]),
         "bsmi_eval_pairs_read": (i32, [p, vp, vp, vp, C.c_uint64, vp, vp]),
         "bsmi_eval_status": (i32, [p, vp]),

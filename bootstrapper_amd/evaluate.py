@@ -1,5 +1,5 @@
-"""`bs evaluate`: scores of segmentations, against ground truth (Rand / VOI) or against the network's own affinities (error
-maps), on the device.
+"""`bs evaluate`: scores of segmentations, against ground truth (Rand / VOI) or against the network's own output (error maps
+against its affinities, or, opt-in, against its local shape descriptors), on the device.
 
 Same command, flags, modes, config keys, dataset discovery, output datasets and JSON as the reference's bootstrapper/evaluate.py
 (`get_seg_datasets` :16-21, `get_eval_config` :24-36, `run_gt_evaluation` :39-64, `run_pred_evaluation` :67-101,
@@ -7,11 +7,17 @@ Same command, flags, modes, config keys, dataset discovery, output datasets and 
 
   pred mode  the pred layer and the mask layer are read once and every segmentation is scored against them
              (csrc/eval.hip `bsmi_eval_aff_errors_u8`: diff, per-chunk maximum, both u8 outputs and the histograms that
-             give the statistics exactly); the outputs are written behind the next layer's work
+             give the statistics exactly); the outputs are written behind the next layer's work.  A `3d_lsds` pred dataset
+             takes the LSD form (`bsmi_eval_lsd_errors_u8`, gp/add_lsd_errors.py) when `[pred] lsd_errors = true` or
+             `--lsd_errors` opts in: per chunk, over the chunk grown by `lsd_margin` (default (2, 50, 50) voxels, the
+             reference's chunk + (4, 100, 100) request), the segmentation's own descriptors (sigma = `lsd_sigma` of
+             [pred.params], else int(voxel_size[-1] * 10); downsample 2), the diff against pred, one maximum, the threshold,
+             the in-plane opening and z closing, then the crop to the chunk.  The lsd package is restated (oracle/lsd_ref.py,
+             tests/lsd_errors_ref.py), not pinned: that is why the form is opt-in
   gt mode    (gt, seg) pair counts per tile on the device (`bsmi_eval_pairs_u64`), merged on the host in exact integers;
              Rand / VOI from the merged table in float64, in ascending (gt, seg) order
 
-Not part of this engine, refused before any work: `3d_lsds` pred datasets (LSD error maps) and `gt.skeletons_file` (ERL).
+Not part of this engine, refused before any work: `3d_lsds` pred datasets without the opt-in, and `gt.skeletons_file` (ERL).
 One deliberate difference: an `out_result` that would overwrite the config file (a config name without `.toml`) is refused.
 """
 import concurrent.futures as cf
@@ -32,7 +38,13 @@ DEFAULT_NEIGHBORHOOD = [[1, 0, 0], [0, 1, 0], [0, 0, 1], [2, 0, 0], [0, 8, 0], [
 DEFAULT_THRESHOLDS = [0.1, 1.0]
 PAIR_CAPACITY = 1 << 22      # slots of the device pair table (3 x 32 MiB + the read-out buffers)
 GT_TILE_VOXELS = 1 << 24     # voxels of one gt-mode tile before any halving on overflow
+LSD_SCRATCH_BYTES = 1 << 30  # device scratch of the LSD form: a layer's chunks go through in groups that stay below this
 WRITES_IN_FLIGHT = 8         # output pieces queued behind the device
+LSD_DOWNSAMPLE = 2           # eval/compute_errors.py:159
+LSD_MARGIN = [2, 50, 50]     # (input_shape - output_shape) / 2 of eval/compute_errors.py:89-90, voxels
+LSD_BLOCK_CELLS = (2, 8, 16)  # lsd_desc_kernel: cells of one block; its window and weight tables share LSD_LDS_BYTES
+LSD_LDS_BYTES = 72704
+LSD_REFUSAL = "3d_lsds error maps are not part of this engine (affinities only)"
 
 
 def get_seg_datasets(seg_datasets_prefix):
@@ -65,8 +77,9 @@ def _check_scope(config, mode):
         pred_dataset = config["pred"]["pred_dataset"]
         name = os.path.basename(pred_dataset.rstrip("/"))
         if "3d_lsds" in name:
-            raise NotImplementedError(f"{pred_dataset}: 3d_lsds error maps are not part of this engine (affinities only)")
-        if "3d_affs" not in name:
+            if not config["pred"].get("lsd_errors"):
+                raise NotImplementedError(f"{pred_dataset}: {LSD_REFUSAL}; opt in with [pred] lsd_errors = true or --lsd_errors")
+        elif "3d_affs" not in name:
             raise ValueError(f"Unknown type for {pred_dataset}")
 
 
@@ -89,14 +102,15 @@ def _same_voxel_size(named):
 
 
 def _read_padded(ds, begin, shape, dtype):
-    """ds[begin : begin + shape] (spatial) as `dtype`, zeros beyond the dataset (gp.Pad)"""
-    out = np.zeros(shape, dtype=dtype)
+    """ds[..., begin : begin + shape] (spatial; every channel) as `dtype`, zeros beyond the dataset (gp.Pad)"""
+    lead = (slice(None),) * (len(ds.shape) - 3)
+    out = np.zeros(list(ds.shape[:-3]) + list(shape), dtype=dtype)
     lo = [max(0, b) for b in begin]
     hi = [min(n, b + s) for n, b, s in zip(ds.shape[-3:], begin, shape)]
     if any(h <= l for l, h in zip(lo, hi)):
         return out
-    key = tuple(slice(l, h) for l, h in zip(lo, hi))
-    dst = tuple(slice(l - b, h - b) for l, h, b in zip(lo, hi, begin))
+    key = lead + tuple(slice(l, h) for l, h in zip(lo, hi))
+    dst = lead + tuple(slice(l - b, h - b) for l, h, b in zip(lo, hi, begin))
     if ds.dtype == dtype:
         ds.read_into(key, out[dst])
     else:
@@ -154,6 +168,30 @@ class EvalDevice:
             self.h, ptr(seg_t), L.i64x3(seg_t.shape), L.i64x3(seg_origin), ptr(pred_t), int(pred_t.shape[0]),
             L.i64x3(pred_t.shape[1:]), ptr(mask_t), offs, L.i64x3(chunk),
             float(thresholds[0]), float(thresholds[1]), int(count_z_end), ptr(emap_t), ptr(emask_t), ptr(hist_t), self.stream))
+
+    def lsd_errors(self, seg_t, seg_origin, pred_t, mask_t, tile, chunk, lsd, thresholds, count_z_end, emap_t, emask_t, hist_t,
+                   debug=None, scratch_bytes=LSD_SCRATCH_BYTES):
+        """lsd: lsd_setup()'s dict.  debug: lsd_debug_buffers() or None"""
+        L = self.lib
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])  # noqa: E731
+        dbg = debug or {}
+        L.check(L.lib.bsmi_eval_lsd_errors_u8(
+            self.h, ptr(seg_t), L.i64x3(seg_t.shape), L.i64x3(seg_origin), ptr(pred_t), ptr(mask_t), L.i64x3(tile), L.i64x3(chunk),
+            L.i64x3(lsd["margin"]), L.i64x3(lsd["context"]), f3(lsd["sigma"]), f3(lsd["voxel_size"]), int(lsd["downsample"]),
+            float(thresholds[0]), float(thresholds[1]), int(count_z_end), int(scratch_bytes), ptr(emap_t), ptr(emask_t), ptr(hist_t),
+            ptr(dbg.get("desc")), ptr(dbg.get("diff")), ptr(dbg.get("max")), ptr(dbg.get("raw")), self.stream))
+
+    def lsd_debug_buffers(self, tile, chunk, margin):
+        """the per-stage outputs of lsd_errors, per chunk over its grown region, chunks in the order (jz * ncy + jy) * ncx + jx"""
+        torch = self.torch
+        c = [min(a, b) for a, b in zip(chunk, tile)]
+        n = int(np.prod([-(-t // k) for t, k in zip(tile, c)]))
+        g = [k + 2 * m for k, m in zip(c, margin)]
+        return {"desc": torch.zeros([n, 10] + g, dtype=torch.float32, device=self.dev),
+                "diff": torch.zeros([n] + g, dtype=torch.float32, device=self.dev),
+                "max": torch.zeros([n], dtype=torch.float32, device=self.dev),
+                "raw": torch.zeros([n] + g, dtype=torch.uint8, device=self.dev)}
 
     def pairs(self, gt_t, seg_t, mask_t):
         """-> (gt ids, seg ids, counts) of one tile (u64 numpy, unordered); raises BsmiError(ERR_OVERFLOW) if the table is full"""
@@ -306,28 +344,68 @@ class _Writes:
             self.pool.shutdown(wait=True)
 
 
+def lsd_setup(voxel_size, lsd_sigma=None, lsd_margin=None, downsample=LSD_DOWNSAMPLE):
+    """the LSD form's parameters as eval/compute_errors.py:60 and AddLSDErrors.setup / prepare derive them: one sigma for the
+    three axes, the context 3 sigma in world units snapped to voxels by shrinking"""
+    sigma = lsd_sigma if lsd_sigma is not None else int(voxel_size[-1] * 10)
+    if isinstance(sigma, (list, tuple)) or not sigma > 0:
+        raise ValueError(f"lsd_sigma must be one positive number (got {sigma!r})")
+    margin = [int(m) for m in (lsd_margin if lsd_margin is not None else LSD_MARGIN)]
+    if len(margin) != 3 or min(margin) < 0:
+        raise ValueError(f"lsd_margin must be three non-negative voxel counts (got {lsd_margin!r})")
+    return {"sigma": [sigma] * 3, "voxel_size": [int(v) for v in voxel_size], "downsample": int(downsample), "margin": margin,
+            "context": [int(math.floor(3 * sigma / v)) for v in voxel_size]}
+
+
+def lsd_check_geometry(lsd, chunk, what):
+    """what the lsd package asserts and what lsd_desc_kernel can hold, as a ValueError before anything is written"""
+    df = lsd["downsample"]
+    for d, ax in enumerate("zyx"):
+        grown = chunk[d] + 2 * lsd["margin"][d]
+        if grown % df:
+            raise ValueError(f"{what}: chunk + 2 * lsd_margin = {grown} voxels along {ax} is not a multiple of the downsample factor {df}")
+        if lsd["context"][d] % df:
+            raise ValueError(f"{what}: the context floor(3 * sigma / voxel_size) = {lsd['context'][d]} voxels along {ax} is not a multiple of "
+                             f"the downsample factor {df}")
+    r = [int(3.0 * (s / (v * df)) + 0.5) for s, v in zip(lsd["sigma"], lsd["voxel_size"])]
+    # weight tables (z, y: 3 per tap; x: 3 x 64 partial sums per group of 6 taps) in float64, then the window and its pad
+    need = 8 * (3 * (2 * r[0] + 1 + 2 * r[1] + 1) + 192 * -(-(2 * r[2] + 1) // 6)) + 4 * (int(np.prod([b + 2 * x for b, x in zip(LSD_BLOCK_CELLS, r)])) + 8)
+    if need > LSD_LDS_BYTES or max(r) > 512:
+        raise ValueError(f"{what}: the LSD window radius {r} (sub-grid cells) is above the kernel's limit: its window needs {need} bytes "
+                         f"of LDS, {LSD_LDS_BYTES} are there")
+
+
 def compute_errors(seg_datasets, pred_dataset, mask_dataset, out_datasets, thresholds=(0.1, 1.0), roi_offset=None, roi_shape=None,
-                   aff_neighborhood=None, device=0, engine=None, whole_roi=False, **kwargs):
-    """eval/compute_errors.py:25-223 (affinity form) for several segmentations at once: out_datasets[i] = (error_map,
-    error_mask) dataset paths of seg_datasets[i].  -> [(error_map stats, error_mask stats)] per segmentation.
+                   aff_neighborhood=None, device=0, engine=None, whole_roi=False, lsd_errors=False, lsd_sigma=None, lsd_margin=None,
+                   **kwargs):
+    """eval/compute_errors.py:25-223 for several segmentations at once: out_datasets[i] = (error_map, error_mask) dataset
+    paths of seg_datasets[i].  -> [(error_map stats, error_mask stats)] per segmentation.  The dataset's name chooses the form:
+    `3d_affs` the affinity form, `3d_lsds` the LSD form (only with lsd_errors = True).
     One layer of chunks is on the device at a time; whole_roi = True hands the whole ROI over as one tile (same outputs)."""
     pred_ds = open_ds(pred_dataset)
     name = os.path.basename(pred_dataset.rstrip("/"))
-    if "3d_lsds" in name:
-        raise NotImplementedError(f"{pred_dataset}: 3d_lsds error maps are not part of this engine (affinities only)")
-    if "3d_affs" not in name:
+    is_lsd = "3d_lsds" in name
+    if is_lsd and not lsd_errors:
+        raise NotImplementedError(f"{pred_dataset}: {LSD_REFUSAL}; opt in with [pred] lsd_errors = true or --lsd_errors")
+    if not is_lsd and "3d_affs" not in name:
         raise ValueError(f"Unknown type for {pred_dataset}")
     if pred_ds.dtype != np.uint8:
         raise ValueError(f"{pred_dataset}: pred datasets must be uint8 (got {pred_ds.dtype})")
     if len(pred_ds.shape) != 4:
         raise ValueError(f"{pred_dataset}: expected [channels][z][y][x], got shape {pred_ds.shape}")
     K = pred_ds.shape[0]
-    nhood = [list(map(int, o)) for o in (aff_neighborhood if aff_neighborhood is not None else DEFAULT_NEIGHBORHOOD)]
-    if len(nhood) < K:
-        raise ValueError(f"aff_neighborhood has {len(nhood)} offsets, {pred_dataset} has {K} channels")
-    nhood = nhood[:K]
-    if K > 16:
-        raise ValueError(f"{pred_dataset}: at most 16 affinity channels")
+    nhood = lsd = None
+    if is_lsd:
+        if K != 10:
+            raise ValueError(f"{pred_dataset}: an LSD pred dataset has 10 channels (got {K})")
+        lsd = lsd_setup(pred_ds.voxel_size, lsd_sigma, lsd_margin)
+    else:
+        nhood = [list(map(int, o)) for o in (aff_neighborhood if aff_neighborhood is not None else DEFAULT_NEIGHBORHOOD)]
+        if len(nhood) < K:
+            raise ValueError(f"aff_neighborhood has {len(nhood)} offsets, {pred_dataset} has {K} channels")
+        nhood = nhood[:K]
+        if K > 16:
+            raise ValueError(f"{pred_dataset}: at most 16 affinity channels")
     seg_dss = [open_ds(s) for s in seg_datasets]
     mask_ds = None if mask_dataset is None else open_ds(mask_dataset)
     _same_voxel_size([(pred_dataset, pred_ds), (mask_dataset, mask_ds)] + list(zip(seg_datasets, seg_dss)))
@@ -339,6 +417,10 @@ def compute_errors(seg_datasets, pred_dataset, mask_dataset, out_datasets, thres
         if roi_offset is not None:
             roi = _intersect((list(roi_offset), list(roi_shape)), roi)
         rois.append(roi)
+    if lsd is not None:
+        for sd_name, roi in zip(seg_datasets, rois):
+            shape = [s // v for s, v in zip(roi[1], vs)]
+            lsd_check_geometry(lsd, [min(c, n) for c, n in zip(pred_ds.chunks[1:], shape)], f"{sd_name} against {pred_dataset}")
     shape_groups = {}
     for i, roi in enumerate(rois):   # segmentations over the same ROI share the pred / mask reads
         shape_groups.setdefault((tuple(roi[0]), tuple(roi[1])), []).append(i)
@@ -347,12 +429,13 @@ def compute_errors(seg_datasets, pred_dataset, mask_dataset, out_datasets, thres
     for (off, size), members in shape_groups.items():
         roi = (list(off), list(size))
         for i, st in zip(members, _errors_over_roi(eng, pred_ds, mask_ds, mask_dataset, [seg_dss[i] for i in members],
-                                                   [out_datasets[i] for i in members], roi, nhood, thresholds, whole_roi)):
+                                                   [out_datasets[i] for i in members], roi, nhood, thresholds, whole_roi, lsd)):
             results[i] = st
     return results
 
 
-def _errors_over_roi(eng, pred_ds, mask_ds, mask_name, seg_dss, outs, roi, nhood, thresholds, whole_roi=False):
+def _errors_over_roi(eng, pred_ds, mask_ds, mask_name, seg_dss, outs, roi, nhood, thresholds, whole_roi=False, lsd=None):
+    """lsd = None: the affinity form with the neighbourhood nhood; else the LSD form with lsd_setup()'s parameters"""
     torch = eng.torch
     vs = pred_ds.voxel_size
     shape = [s // v for s, v in zip(roi[1], vs)]
@@ -361,8 +444,14 @@ def _errors_over_roi(eng, pred_ds, mask_ds, mask_name, seg_dss, outs, roi, nhood
     if shape[1] > (1 << 20) or shape[2] > (1 << 20):
         raise ValueError(f"ROI {shape} voxels: rows and sections beyond 2^20 voxels are not supported")
     chunk = [min(c, n) for c, n in zip(pred_ds.chunks[1:], shape)]
-    neg = [min([0] + [o[d] for o in nhood]) for d in range(3)]
-    pos = [max([0] + [o[d] for o in nhood]) for d in range(3)]
+    if lsd is None:
+        grow = [0, 0, 0]   # pred and mask cover the tile itself
+        neg = [min([0] + [o[d] for o in nhood]) for d in range(3)]
+        pos = [max([0] + [o[d] for o in nhood]) for d in range(3)]
+    else:
+        grow = lsd["margin"]   # they cover every chunk's grown region, the segmentation its label array
+        pos = [m + c for m, c in zip(lsd["margin"], lsd["context"])]
+        neg = [-p for p in pos]
     outs_ds = []
     for sd, (map_path, mask_path) in zip(seg_dss, outs):
         keep = dict(shape=shape, offset=roi[0], voxel_size=vs, axis_names=sd.axis_names[-3:], units=sd.units[-3:],
@@ -381,24 +470,34 @@ def _errors_over_roi(eng, pred_ds, mask_ds, mask_name, seg_dss, outs, roi, nhood
             if li + 1 == len(zs) and len(zs) > 1:
                 writes.drain()   # the snapped last layer shares a chunk with the one before: no two writers on one chunk
             tile = [tz, shape[1], shape[2]]
-            pred = np.empty([pred_ds.shape[0]] + tile, np.uint8)
-            pred_ds.read_into((slice(None), slice(pb[0] + z, pb[0] + z + tz), slice(pb[1], pb[1] + shape[1]),
-                               slice(pb[2], pb[2] + shape[2])), pred)
+            grown = [t + 2 * g for t, g in zip(tile, grow)]
+            if lsd is None:
+                pred = np.empty([pred_ds.shape[0]] + tile, np.uint8)
+                pred_ds.read_into((slice(None), slice(pb[0] + z, pb[0] + z + tz), slice(pb[1], pb[1] + shape[1]),
+                                   slice(pb[2], pb[2] + shape[2])), pred)
+            else:   # real values inside the dataset, also outside the ROI; zeros beyond it (gp.Pad(pred, None))
+                pred = _read_padded(pred_ds, [pb[0] + z - grow[0], pb[1] - grow[1], pb[2] - grow[2]], grown, np.uint8)
             pred_t = eng.to_dev(pred)
             mask_t = None
             if mask_ds is not None:
-                mask_t = eng.to_dev(_as_mask_u8(_read_padded(mask_ds, [mb[0] + z, mb[1], mb[2]], tile, mask_ds.dtype), mask_name))
+                mask_t = eng.to_dev(_as_mask_u8(_read_padded(mask_ds, [mb[0] + z - grow[0], mb[1] - grow[1], mb[2] - grow[2]], grown,
+                                                             mask_ds.dtype), mask_name))
             for sd, sb, hist, (map_ds, msk_ds) in zip(seg_dss, sbs, hists, outs_ds):
                 seg_shape = [t - n + p for t, n, p in zip(tile, neg, pos)]
                 seg = _read_padded(sd, [sb[0] + z + neg[0], sb[1] + neg[1], sb[2] + neg[2]], seg_shape, np.uint64)
                 seg_t = eng.to_dev(seg)
                 emap_t = torch.empty(tile, dtype=torch.uint8, device=eng.dev)
                 emask_t = torch.empty(tile, dtype=torch.uint8, device=eng.dev)
-                eng.aff_errors(seg_t, neg, pred_t, mask_t, nhood, chunk, thresholds, keep_z, emap_t, emask_t, hist)
+                if lsd is None:
+                    eng.aff_errors(seg_t, neg, pred_t, mask_t, nhood, chunk, thresholds, keep_z, emap_t, emask_t, hist)
+                else:
+                    eng.lsd_errors(seg_t, neg, pred_t, mask_t, tile, chunk, lsd, thresholds, keep_z, emap_t, emask_t, hist)
                 key = (slice(z, z + keep_z), slice(0, shape[1]), slice(0, shape[2]))
                 writes.submit(map_ds, key, emap_t[:keep_z].cpu().numpy())
                 writes.submit(msk_ds, key, emask_t[:keep_z].cpu().numpy())
         writes.drain()
+        if lsd is not None:
+            eng.lib.check(eng.lib.lib.bsmi_eval_status(eng.h, eng.stream))   # more distinct labels than the id table holds
     finally:
         writes.close()
     out = []
@@ -423,7 +522,8 @@ def run_pred_evaluations(config, seg_datasets, device=0, engine=None):
     params = config["pred"].get("params", {})
     mask_dataset = config.get("mask_dataset")
     outs = [_pred_outputs(s, pred_dataset) for s in seg_datasets]
-    stats = compute_errors(seg_datasets, pred_dataset, mask_dataset, outs, thresholds=thresholds, device=device, engine=engine, **params)
+    stats = compute_errors(seg_datasets, pred_dataset, mask_dataset, outs, thresholds=thresholds, device=device, engine=engine,
+                           lsd_errors=bool(config["pred"].get("lsd_errors", False)), **params)
     entries = []
     for seg_ds, (map_ds, mask_ds), (map_stats, mask_stats) in zip(seg_datasets, outs, stats):
         # the reference's dict literal names "mask_ds" twice: the key keeps its first place and takes the error-mask path
@@ -437,7 +537,10 @@ def run_pred_evaluation(config, seg_ds, device=0, engine=None):
 
 
 def run_evaluation(config_file, mode="pred", device=0, **kwargs):
+    lsd_errors = kwargs.pop("lsd_errors", None)
     config = get_eval_config(config_file, mode, **kwargs)
+    if lsd_errors and mode == "pred":
+        config.setdefault("pred", {})["lsd_errors"] = True
     out_result = kwargs.get("out_result") or config["out_result"]
     if os.path.abspath(out_result) == os.path.abspath(config_file):
         raise ValueError(f"out_result {out_result} would overwrite the config file: name the config 04_eval_*.toml or pass --out_result")
@@ -483,7 +586,8 @@ def eval_modes(config_file, gt=False, pred=False):
 @click.option("--gt", "-gt", is_flag=True, help="Evaluate only against ground-truth")
 @click.option("--pred", "-p", is_flag=True, help="Evaluate only against predictions")
 @click.option("--out_result", "-o", type=click.Path())
-def evaluate(config_file, gt, pred, out_result=None):
+@click.option("--lsd_errors", is_flag=True, help="Score against a 3d_lsds pred dataset (LSD error maps; same as [pred] lsd_errors = true)")
+def evaluate(config_file, gt, pred, out_result=None, lsd_errors=False):
     """Evaluate segmentations as specified in the config file."""
     for mode in eval_modes(config_file, gt, pred):
-        run_evaluation(config_file, mode, out_result=out_result)
+        run_evaluation(config_file, mode, out_result=out_result, lsd_errors=lsd_errors or None)

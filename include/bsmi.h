@@ -538,6 +538,39 @@ int bsmi_eval_aff_errors_u8(bsmi_eval *h, const uint64_t *seg_dev, const int64_t
                             const int32_t *offsets, const int64_t chunk_shape[3], float floor_, float ceil_, int64_t count_z_end,
                             uint8_t *error_map_dev, uint8_t *error_mask_dev, uint64_t *hist_dev, void *stream);
 
+/* LSD errors of a tile of Scan chunks (gp/add_lsd_errors.py as eval/compute_errors.py:149-177 calls it), chunk by chunk as
+ * the reference's `process` does, over the chunk grown by `margin` voxels per side (region G; the reference requests
+ * chunk + (4, 100, 100), margin (2, 50, 50); (0, 0, 0) is the bare chunk):
+ *   a    = the 10 local shape descriptors of the segmentation over G (gaussian mode, all components), from the label array
+ *          L = G grown by `context` = floor(3 sigma / voxel_size) voxels per side: windows on the sub-grid L[::downsample]
+ *          anchored at L's first voxel, weights as scipy.ndimage.gaussian_filter(mode="constant", truncate=3.0) builds them,
+ *          float64 accumulation, variances clamped at 1e-3, clipped to [0, 1], 0 on background (the arithmetic of
+ *          bsmi_train_lsd_targets; the lsd package is restated, parity unpinned)
+ *   diff = ((a_0 - p_0)^2 + (a_1 - p_1)^2) + ... over the 10 channels in f32 without contraction, p_c = float(pred[c]) *
+ *          float(1/255), (* float(mask) when mask_dev is given);  d = diff / max(diff over G) (0 when that is 0)
+ *   raw  = floor < d < ceil over G; opened in the plane by the L1 diamond of radius 4 (= binary_erosion then binary_dilation
+ *          with the 4-neighbour cross, iterations = 4), then closed along z by the 3-column, every step with 0 outside G
+ *   error_map = u8(trunc(d * 255)), error_mask = the closed mask, both cropped to the chunk
+ * seg_dev: u64 [seg_shape], seg_origin = its first voxel relative to the tile's (<= -(margin + context)); it must hold the
+ * tile grown by margin + context (zeros beyond the dataset).  pred_dev u8 [10][tile + 2 margin], mask_dev u8 [tile + 2 margin]
+ * or NULL (zeros beyond their datasets).  chunk + 2 margin and context must be multiples of downsample on every axis, and the
+ * window radii round(3 sigma / (voxel_size downsample)) must fit the descriptor kernel's LDS window ((2 + 2 rz) (8 + 2 ry)
+ * (16 + 2 rx) cells of 4 bytes plus the weight tables in 71 KiB), else BSMI_ERR_INVALID.  downsample is 1 or 2.  Chunk placement, ownership of
+ * overlapped voxels, hist_dev and count_z_end as in bsmi_eval_aff_errors_u8.  Labels become 32-bit ids through an id table of
+ * the handle's pair_capacity slots; more distinct labels than it holds set the overflow flag (bsmi_eval_status).  The chunks
+ * are processed in groups whose scratch (per chunk 4 B per sub-grid cell of L and 7 B per voxel of G) stays below
+ * scratch_limit_bytes; a single chunk above it is BSMI_ERR_INVALID.
+ * Debug outputs (NULL in production), per chunk over its region G, chunks in the order (jz * ncy + jy) * ncx + jx:
+ * debug_desc_dev f32 [chunks][10][G], debug_diff_dev f32 [chunks][G] (before normalisation), debug_max_dev f32 [chunks],
+ * debug_raw_mask_dev u8 [chunks][G] (before the morphology). */
+int bsmi_eval_lsd_errors_u8(bsmi_eval *h, const uint64_t *seg_dev, const int64_t seg_shape[3], const int64_t seg_origin[3],
+                            const uint8_t *pred_dev, const uint8_t *mask_dev, const int64_t tile_shape[3],
+                            const int64_t chunk_shape[3], const int64_t margin[3], const int64_t context[3], const float sigma[3],
+                            const float voxel_size[3], int downsample, float floor_, float ceil_, int64_t count_z_end,
+                            uint64_t scratch_limit_bytes, uint8_t *error_map_dev, uint8_t *error_mask_dev, uint64_t *hist_dev,
+                            float *debug_desc_dev, float *debug_diff_dev, float *debug_max_dev, uint8_t *debug_raw_mask_dev,
+                            void *stream);
+
 /* Adds a tile's (gt, seg) voxel pairs to the handle's pair table (reset != 0 empties it first).  gt_dev, seg_dev u64
  * [shape]; mask_dev u8 [shape] or NULL: both ids are multiplied by the mask value first, wrapping at 2^64, as the reference
  * does.  Voxels whose (masked) gt id is 0 are left out; seg id 0 is an ordinary label.  Runs of equal pairs along x are

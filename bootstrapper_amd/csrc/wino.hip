@@ -14,6 +14,7 @@
 // form on the full-size block: DESIGN.md section 4.
 #include "wino.h"
 
+#include <cstdlib>
 #include <cstring>
 
 #include "dev_guard.h"  // last: routes hipMalloc / hipFree through the guarded allocator (BSMI_GUARD_MB)
@@ -413,18 +414,47 @@ __device__ __forceinline__ void store_split4(uint16_t* base, size_t e, int hf, c
   *(u32x2_t*)p = hv;
   *(u32x2_t*)(p + 8) = lv;
 }
+// The same for the two lanes 2k (hf 0) and 2k + 1 (hf 1) that hold the halves of ONE 8-channel group, as ONE 16-byte store
+// per lane instead of two 8-byte ones: lane hf 0 writes the whole hi vector, lane hf 1 the whole lo vector, after the lanes
+// have exchanged the halves they do not own (DPP quad_perm [1, 0, 3, 2]).  p = base + 2 e + 8 hf; both lanes of a pair must
+// be active and at the same e (they are: a tile has an even number of channel groups).  Nontemporal: V, 0.2 to 3 GB a launch,
+// is read next by the GEMM and not by this kernel; measured with plain stores the two kernels take 8 % longer (DESIGN.md
+// section 4).
+__device__ __forceinline__ uint32_t swap_pair(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false); }
+__device__ __forceinline__ void store_split4_pair(uint16_t* p, int hf, const float* f) {
+  uint16_t hb[4], lb[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    hb[k] = to_bf16(f[k]);
+    lb[k] = to_bf16(f[k] - __uint_as_float((uint32_t)hb[k] << 16));
+  }
+  const u32x2_t hv = {(uint32_t)hb[0] | ((uint32_t)hb[1] << 16), (uint32_t)hb[2] | ((uint32_t)hb[3] << 16)};
+  const u32x2_t lv = {(uint32_t)lb[0] | ((uint32_t)lb[1] << 16), (uint32_t)lb[2] | ((uint32_t)lb[3] << 16)};
+  const uint32_t r0 = swap_pair(hf ? hv.x : lv.x), r1 = swap_pair(hf ? hv.y : lv.y);
+  const u32x4_t o = {hf ? r0 : hv.x, hf ? r1 : hv.y, hf ? lv.x : r0, hf ? lv.y : r1};
+  __builtin_nontemporal_store(o, (u32x4_t*)p);
+}
 
-// One thread: 4 channels along one row of tiles (z, ty); neighbouring tiles share two of their six input columns, whose
-// row transforms are kept.  Rows / columns past the source (overhanging last tiles) are clamped: whatever they hold only
-// reaches outputs that are never stored.
-__global__ __launch_bounds__(256) void wino4_in_kernel(const WinoInArgs a, int src, size_t total) {
+// One thread: 4 channels of a SEGMENT of S consecutive tiles of one row of tiles (z, ty), tiles [sg S, min(sg S + S, Tx));
+// neighbouring tiles share two of their six input columns, whose row transforms are kept inside the segment (a segment's
+// first two columns are its left neighbour's last two, read again: the neighbour has just had them, they come from L2).
+// Thread order: channel group fastest, then segment, tile row, z -- the lanes of a wave write contiguous runs of each V
+// plane, and with few channel groups a wave covers adjacent tiles.  S = Tx, nseg = 1 is the whole-row decomposition the
+// kernel had before; the arithmetic of a tile does not depend on S (V is the same bit for bit; launch_wino_in picks S).
+// Rows / columns past the source (overhanging last tiles) are clamped: whatever they hold only reaches outputs that are
+// never stored.  The 36 planes of V are walked with ONE running pointer: as 36 offsets from the tile's element they were
+// hoisted out of the tile loop, 72 registers that kept the kernel at 256 + 12 registers and one wave per SIMD (now 202 and
+// two, which the launch bounds ask for: one wave per SIMD is 20 % slower at S = 1).
+__global__ __launch_bounds__(256, 2) void wino4_in_kernel(const WinoInArgs a, int src, size_t total, int S, int nseg) {
   const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const unsigned blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   const size_t i = (size_t)blk * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int ncg = a.Cpad[src] >> 2;
   const int cg = (int)(i % ncg), cv = cg >> 1, hf = cg & 1;
-  const size_t t = i / ncg;
+  size_t t = i / ncg;
+  const int tx0 = (int)(t % nseg) * S, tx1 = tx0 + S < a.Tx ? tx0 + S : a.Tx;
+  t /= nseg;
   const int ty = (int)(t % a.Ty);
   const int z = (int)(t / a.Ty);
   const uint16_t* sp = (const uint16_t*)a.src[src];
@@ -436,7 +466,6 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const WinoInArgs a, int s
     y = y < H - 1 ? y : H - 1;
     erow[rr] = (((size_t)(z + a.oz[src]) * H + y) * W) * C + 8 * cv;
   }
-  uint16_t* V = (uint16_t*)a.V;
   const size_t plane = (size_t)a.Dv * a.Ty * a.Tx * a.Cv;
   const size_t e_out = (((size_t)z * a.Ty + ty) * a.Tx) * a.Cv + a.cv0[src] + 8 * cv;
   float col[6][6][4];  // col[c][xi]: (B^T d)[xi] of input column 4 tx + c
@@ -448,12 +477,13 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const WinoInArgs a, int s
     for (int rr = 0; rr < 6; ++rr) load_split4(sp, erow[rr] + (size_t)x * C, hf, d[rr]);
     bt4_apply(d, col[c]);
   };
-  load_col(0, 0);
-  load_col(1, 1);
-  for (int tx = 0; tx < a.Tx; ++tx) {
+  load_col(0, 4 * tx0);
+  load_col(1, 4 * tx0 + 1);
+  uint16_t* vt = (uint16_t*)a.V + 2 * (e_out + (size_t)tx0 * a.Cv) + 8 * hf;
+  for (int tx = tx0; tx < tx1; ++tx) {
 #pragma unroll
     for (int c = 2; c < 6; ++c) load_col(c, 4 * tx + c);
-    const size_t e0 = e_out + (size_t)tx * a.Cv;
+    uint16_t* vp = vt;   // walks the 36 planes of V: one running pointer, not 36 addresses kept across the tiles of a segment
 #pragma unroll
     for (int xi = 0; xi < 6; ++xi) {
       float in[6][4], v[6][4];
@@ -463,8 +493,12 @@ __global__ __launch_bounds__(256) void wino4_in_kernel(const WinoInArgs a, int s
         for (int k = 0; k < 4; ++k) in[c][k] = col[c][xi][k];
       bt4_apply(in, v);
 #pragma unroll
-      for (int nu = 0; nu < 6; ++nu) store_split4(V, (size_t)(6 * xi + nu) * plane + e0, hf, v[nu]);
+      for (int nu = 0; nu < 6; ++nu) {
+        store_split4_pair(vp, hf, v[nu]);
+        vp += 2 * plane;
+      }
     }
+    vt += 2 * a.Cv;
 #pragma unroll
     for (int xi = 0; xi < 6; ++xi)
 #pragma unroll
@@ -493,15 +527,18 @@ __host__ __device__ constexpr float tu4(int par, int xi, int k) {  // (B^T U_par
   for (int r = 0; r < 6; ++r) s += bt4(xi, r) * up4(par, r, k);
   return s;
 }
+// Segments of S tiles as in wino4_in_kernel; a segment reads its first THREE window columns itself.
 template <int PY, int PX>
-__global__ __launch_bounds__(256) void wino4_in_up_kernel(const WinoInArgs a, int src, size_t total) {
+__global__ __launch_bounds__(256, 2) void wino4_in_up_kernel(const WinoInArgs a, int src, size_t total, int S, int nseg) {
   const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const unsigned blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   const size_t i = (size_t)blk * blockDim.x + threadIdx.x;
   if (i >= total) return;
   const int ncg = a.Cpad[src] >> 2;
   const int cg = (int)(i % ncg), cv = cg >> 1, hf = cg & 1;
-  const size_t t = i / ncg;
+  size_t t = i / ncg;
+  const int tx0 = (int)(t % nseg) * S, tx1 = tx0 + S < a.Tx ? tx0 + S : a.Tx;
+  t /= nseg;
   const int ty = (int)(t % a.Ty);
   const int z = (int)(t / a.Ty);
   const uint16_t* sp = (const uint16_t*)a.src[src];
@@ -515,7 +552,6 @@ __global__ __launch_bounds__(256) void wino4_in_up_kernel(const WinoInArgs a, in
     wy[k] = y < 0 ? 0 : (y > H - 1 ? H - 1 : y);
   }
   const int bx = (a.ox[src] >> 1) - 1 + PX;
-  uint16_t* V = (uint16_t*)a.V;
   const size_t plane = (size_t)a.Dv * a.Ty * a.Tx * a.Cv;
   const size_t e_out = (((size_t)z * a.Ty + ty) * a.Tx) * a.Cv + a.cv0[src] + 8 * cv;
   float ct[5][6][4];  // ct[c][xi] = sum_k (B^T Uy)[xi][k] L[k][window column c]
@@ -535,13 +571,14 @@ __global__ __launch_bounds__(256) void wino4_in_up_kernel(const WinoInArgs a, in
         ct[c][xi][ch] = acc;
       }
   };
-  load_ct(0, bx);
-  load_ct(1, bx + 1);
-  load_ct(2, bx + 2);
-  for (int tx = 0; tx < a.Tx; ++tx) {
+  load_ct(0, bx + 2 * tx0);
+  load_ct(1, bx + 2 * tx0 + 1);
+  load_ct(2, bx + 2 * tx0 + 2);
+  uint16_t* vt = (uint16_t*)a.V + 2 * (e_out + (size_t)tx0 * a.Cv) + 8 * hf;
+  for (int tx = tx0; tx < tx1; ++tx) {
     load_ct(3, bx + 2 * tx + 3);
     load_ct(4, bx + 2 * tx + 4);
-    const size_t e0 = e_out + (size_t)tx * a.Cv;
+    uint16_t* vp = vt;
 #pragma unroll
     for (int xi = 0; xi < 6; ++xi) {
 #pragma unroll
@@ -555,9 +592,11 @@ __global__ __launch_bounds__(256) void wino4_in_up_kernel(const WinoInArgs a, in
             if (tu4(PX, nu, c) != 0.f) acc += tu4(PX, nu, c) * ct[c][xi][ch];
           v[ch] = acc;
         }
-        store_split4(V, (size_t)(6 * xi + nu) * plane + e0, hf, v);
+        store_split4_pair(vp, hf, v);
+        vp += 2 * plane;
       }
     }
+    vt += 2 * a.Cv;
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -647,6 +686,24 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
 
 }  // namespace
 
+// How the F(4x4) input transforms cut a row of Tx tiles into segments (one thread: 4 channels of one segment).
+// BSMI_WINO_IN_SEG, read once per process: unset = the rule, 0 = whole rows (the decomposition before segments existed, kept
+// as the cross-check), n > 0 = S = min(n, Tx) on every launch.  V does not depend on it, bit for bit.
+// The rule is S = 1, one tile per thread.  Measured on every launch of the 128^3 block, the time rises
+// with S -- S = 1, 2, 3, whole rows: 1.93, 2.08, 2.13, 2.45 ms per block for wino4_in_kernel, 0.80, 0.83, 0.85, 0.87 for
+// wino4_in_up_kernel (with plain stores) -- also on launches that have more than twenty rounds of resident workgroups at any S: what pays is
+// not the balance of the last round but that the 256 threads of a workgroup write one contiguous 4 KB run of each V plane,
+// and that outweighs the columns a segment reads again (all six instead of four per tile, from L2).
+static int wino_in_seg_mode() {
+  static const int m = [] { const char* e = getenv("BSMI_WINO_IN_SEG"); return e ? atoi(e) : -1; }();
+  return m;
+}
+static void wino_in_segments(int Tx, int& S, int& nseg) {
+  const int mode = wino_in_seg_mode();
+  S = mode < 0 ? 1 : mode == 0 ? Tx : mode < Tx ? mode : Tx;
+  nseg = (Tx + S - 1) / S;
+}
+
 int launch_wino_in(const WinoInArgs& a, hipStream_t s) {
   const int m = a.m == 4 ? 4 : 2;
   if (a.m != 0 && a.m != 2 && a.m != 4) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: tile edge %d (2 or 4)", a.m);
@@ -658,22 +715,25 @@ int launch_wino_in(const WinoInArgs& a, hipStream_t s) {
     // F(4x4): the last tile row / column may overhang by up to three voxels (clamped reads); more than that is a planning error
     if (m == 4 && (a.oy[q] < 0 || a.ox[q] < 0 || a.oy[q] + 4 * a.Ty + 2 > a.H[q] * upf + 3 || a.ox[q] + 4 * a.Tx + 2 > a.W[q] * upf + 3))
       BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: F(4x4) tiles leave source %d by more than a tile's overhang", q);
-    const size_t total = (size_t)a.Dv * a.Ty * (a.Cpad[q] / (m == 4 ? 4 : 8));  // one thread per (z, tile row, 8 resp. 4 channels)
+    int S = a.Tx, nseg = 1;
+    if (m == 4) wino_in_segments(a.Tx, S, nseg);
+    // one thread per (z, tile row, 8 channels); F(4x4): per (z, tile row, segment of the row, 4 channels)
+    const size_t total = (size_t)a.Dv * a.Ty * (a.Cpad[q] / (m == 4 ? 4 : 8)) * nseg;
     const dim3 grid((unsigned)((total + 255) / 256));
     if (a.upf[q] > 0) {
       if (a.upf[q] != 2 || a.oy[q] < 0 || a.ox[q] < 0) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: only a factor-2 upsampling can be fused");
       const int par = 2 * (a.oy[q] & 1) + (a.ox[q] & 1);
       if (m == 4) {
-        if (par == 0) hipLaunchKernelGGL((wino4_in_up_kernel<0, 0>), grid, dim3(256), 0, s, a, q, total);
-        else if (par == 1) hipLaunchKernelGGL((wino4_in_up_kernel<0, 1>), grid, dim3(256), 0, s, a, q, total);
-        else if (par == 2) hipLaunchKernelGGL((wino4_in_up_kernel<1, 0>), grid, dim3(256), 0, s, a, q, total);
-        else hipLaunchKernelGGL((wino4_in_up_kernel<1, 1>), grid, dim3(256), 0, s, a, q, total);
+        if (par == 0) hipLaunchKernelGGL((wino4_in_up_kernel<0, 0>), grid, dim3(256), 0, s, a, q, total, S, nseg);
+        else if (par == 1) hipLaunchKernelGGL((wino4_in_up_kernel<0, 1>), grid, dim3(256), 0, s, a, q, total, S, nseg);
+        else if (par == 2) hipLaunchKernelGGL((wino4_in_up_kernel<1, 0>), grid, dim3(256), 0, s, a, q, total, S, nseg);
+        else hipLaunchKernelGGL((wino4_in_up_kernel<1, 1>), grid, dim3(256), 0, s, a, q, total, S, nseg);
       } else if (par == 0) hipLaunchKernelGGL((wino_in_up_kernel<0, 0>), grid, dim3(256), 0, s, a, q, total);
       else if (par == 1) hipLaunchKernelGGL((wino_in_up_kernel<0, 1>), grid, dim3(256), 0, s, a, q, total);
       else if (par == 2) hipLaunchKernelGGL((wino_in_up_kernel<1, 0>), grid, dim3(256), 0, s, a, q, total);
       else hipLaunchKernelGGL((wino_in_up_kernel<1, 1>), grid, dim3(256), 0, s, a, q, total);
     } else if (m == 4) {
-      hipLaunchKernelGGL(wino4_in_kernel, grid, dim3(256), 0, s, a, q, total);
+      hipLaunchKernelGGL(wino4_in_kernel, grid, dim3(256), 0, s, a, q, total, S, nseg);
     } else {
       hipLaunchKernelGGL(wino_in_kernel, grid, dim3(256), 0, s, a, q, total);
     }

@@ -64,6 +64,7 @@ CODEC_RAW, CODEC_ZLIB, CODEC_GZIP, CODEC_ZSTD, CODEC_LZ4, CODEC_BLOSC = range(6)
 BLOSC_LZ4, BLOSC_ZLIB, BLOSC_ZSTD = 1, 3, 4
 CHUNK_MISSING = 1
 MORPH_DILATE, MORPH_ERODE = 0, 1
+RESCALE_DOWN, RESCALE_UP = 0, 1
 
 
 class BsmiError(RuntimeError):
@@ -165,6 +166,11 @@ def _load():
         "bsmi_label_morph_u64": (i32, [i32, vp, i64p, i32, i32, i32, vp, vp, vp]),
         "bsmi_label_fill_holes_scratch_bytes": (C.c_size_t, [i64p, C.c_uint64]),
         "bsmi_label_fill_holes_u64": (i32, [i32, vp, i64p, i32, vp, vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), vp]),
+        "bsmi_mask_closing_work_bytes": (C.c_size_t, [i64p, i32]),
+        "bsmi_mask_closing_disk_u8": (i32, [i32, vp, i64p, i32, vp, vp, C.c_size_t, vp]),
+        "bsmi_downscale_mean": (i32, [i32, vp, i32, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64p, vp]),
+        "bsmi_rescale_sample": (i32, [i32, vp, i32, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, i64p, vp]),
+        "bsmi_nonzero_bbox": (i32, [i32, vp, i32, i64p, i64p, vp, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

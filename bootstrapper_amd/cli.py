@@ -1,5 +1,5 @@
-"""`bs`-compatible command line for the hot path: `train`, `predict`, `segment`, `refine` and `evaluate` with the reference's
-flags (/root/reference/bootstrapper/cli.py:51-92, predict.py:243-266, segment.py:166-241, evaluate.py:130-159).
+"""`bs`-compatible command line for the hot path: `train`, `predict`, `segment`, `refine`, `evaluate` and `utils` with the reference's
+flags (/root/reference/bootstrapper/cli.py:51-92, predict.py:243-266, segment.py:166-241, evaluate.py:130-159, utils.py:9-19).
     python -m bootstrapper_amd.cli predict 02_pred.toml -s 01 -ng 8
     python -m bootstrapper_amd.cli segment 03_seg.toml -ws -p 'thresholds=[0.2,0.5]'
     python -m bootstrapper_amd.cli eval 04_eval_volume.toml
@@ -75,6 +75,10 @@ cli.add_command(_refine, "refine")
 from .evaluate import evaluate as _evaluate  # noqa: E402
 
 cli.add_command(_evaluate, "evaluate")
+
+from .utils import utils  # noqa: E402
+
+cli.add_command(utils)
 
 # aliases of the reference CLI (cli.py:38-44)
 cli.add_command(train, "t")

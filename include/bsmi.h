@@ -625,6 +625,44 @@ int bsmi_label_fill_holes_u64(int device, const uint64_t *in_dev, const int64_t 
                               void *scratch_dev, size_t scratch_bytes, uint64_t table_capacity, uint64_t *n_filled,
                               void *stream);
 
+/* ---- volume utilities (`bs utils`: mask, scale_pyramid, bbox) -------------------------------
+ * Raw mask (reference data/mask.py:15-30): the binary closing of every z section of in_dev u8 [D][H][W] on its own, on
+ * in != 0, by the disk dx^2 + dy^2 <= radius^2 (1 <= radius <= 16), written as 0 / 1 to out_dev.  The closing is that of
+ * the section zero-extended to the infinite plane, restricted to the section:
+ *   out(p) = AND_{q in p + disk} OR_{s in q + disk} x0(s)
+ * i.e. the dilation is evaluated on the section grown by `radius` on every side before it is eroded (equal to skimage's
+ * binary_closing of the section padded with 2 * radius zeros; restated in tests/utils_ref.py).
+ * work_dev: bsmi_mask_closing_work_bytes(shape, radius) bytes on the device, 8-byte aligned (the packed dilation; 0 from
+ * that call = bad arguments).  in_dev is never written; in_dev, out_dev and work_dev must differ (BSMI_ERR_INVALID).  Two
+ * launches, asynchronous on `stream`. */
+size_t bsmi_mask_closing_work_bytes(const int64_t shape[3], int radius);
+int bsmi_mask_closing_disk_u8(int device, const uint8_t *in_dev, const int64_t shape[3], int radius, uint8_t *out_dev,
+                              void *work_dev, size_t work_bytes, void *stream);
+
+/* One level of a scale pyramid (reference data/scale_pyramid.py:31-56) over [D][H][W] arrays.  Output voxel o covers the
+ * input window [o * k - lead, o * k - lead + k) per axis (k = factor, 0 <= lead < k: how far the output grid's origin lies
+ * before the input's, in input voxels); input positions outside in_shape count as 0.
+ *   bsmi_downscale_mean (itemsize 1 | 2: u8, u16; prod k <= 65536 so that the u32 sum is exact):
+ *     out[o] = (sum of the window) / prod k, rounded down -- block_reduce(np.mean) with zero fill, stored as an integer.
+ *   bsmi_rescale_sample (itemsize 1, 2, 4, 8):
+ *     BSMI_RESCALE_DOWN: out[o] = in[o * k + k / 2 - lead] (0 outside): in_data[slice(k // 2, None, k)].
+ *     BSMI_RESCALE_UP:   out[o] = in[o / k]: np.repeat.  lead must be 0 and out_shape <= in_shape * k.
+ * in_dev is never written and must differ from out_dev.  Asynchronous on `stream`. */
+#define BSMI_RESCALE_DOWN 0
+#define BSMI_RESCALE_UP 1
+int bsmi_downscale_mean(int device, const void *in_dev, int itemsize, const int64_t in_shape[3], const int32_t factor[3],
+                        const int32_t lead[3], void *out_dev, const int64_t out_shape[3], void *stream);
+int bsmi_rescale_sample(int device, const void *in_dev, int itemsize, const int64_t in_shape[3], const int32_t factor[3],
+                        const int32_t lead[3], int mode, void *out_dev, const int64_t out_shape[3], void *stream);
+
+/* Bounding box of the non-zero voxels (reference data/bbox.py:45, find_objects(arr > 0); elements are read as unsigned
+ * integers of `itemsize` 1, 2, 4 or 8 bytes).  box_dev int64 [6] = (min z, y, x, max z, y, x): the call merges the
+ * extremes of (z, y, x) + origin over this array's non-zero voxels into what box_dev already holds, so a volume can be
+ * streamed tile by tile; the caller initialises it to (INT64_MAX x 3, -1 x 3), which an all-zero volume leaves as it is.
+ * Asynchronous on `stream`. */
+int bsmi_nonzero_bbox(int device, const void *in_dev, int itemsize, const int64_t shape[3], const int64_t origin[3],
+                      int64_t *box_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

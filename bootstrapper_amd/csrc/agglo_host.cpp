@@ -3,10 +3,10 @@
 // The reference's non-blockwise `bs segment --ws` lets the user pick one of ten
 // OneMinus<HistogramQuantileAffinity<RegionGraphType, Q, ScoreValue, 256, InitWithMax>> scorers besides the mean
 // (/root/reference/bootstrapper/post/watershed.py:230-243) and hands the whole loop to waterz, host C++.  Here the device
-// builds the region graph and the per-edge affinity histograms (seg.hip: agg_edges_kernel, agg_hist_kernel -- the
+// builds the region graph and the per-edge affinity histograms (seg_graph.hip: agg_edges_kernel, agg_hist_kernel -- the
 // bandwidth-bound part) and relabels the volume; the merge loop itself is a sequential priority-queue algorithm over a
 // graph that shrinks as it goes, with a 256-bin histogram added per contraction, and runs here as waterz's does.  Only the
-// mean scorer, the one the blockwise path is restricted to, has a device merge loop (seg.hip: agg_merge_kernel).
+// mean scorer, the one the blockwise path is restricted to, has a device merge loop (seg_graph.hip: agg_merge_kernel).
 //
 // Algorithm: IterativeRegionMerging::mergeUntil / mergeRegions as specified in oracle/seg_ref.c (the same rule the device
 // loop follows): pop by the STORED score, a stale edge is re-scored and pushed back, on a merge the dearer of two edges to a
@@ -152,13 +152,13 @@ extern "C" int bsmi_agglomerate_hist_graph(uint32_t n_nodes, uint32_t n_edges, c
 // ---- blockwise RAG scoring on the host -------------------------------------------------------------------------------
 // post/blockwise/waterz_agglom.py:106-170 scores the edges of a block's region graph by agglomerating it to the end
 // (waterz, OneMinus<MeanAffinity>, discretize_queue bins) and reading every edge's score off the merge tree.  The device
-// builds the graph (seg.hip: rag_ids / agg_edges / rag_compact kernels -- the pass over the 160^3 read box); the merge
-// loop is a sequential queue algorithm over a few thousand edges, which one wave replays in 12 ms per block (seg.hip:
+// builds the graph (seg_graph.hip: rag_ids / agg_edges / rag_compact kernels -- the pass over the 160^3 read box); the merge
+// loop is a sequential queue algorithm over a few thousand edges, which one wave replays in 12 ms per block (seg_graph.hip:
 // rag_merge_kernel, kept: bsmi_rag_merge_scores_u8) and a host core in a fraction of a millisecond.  The block pipeline
 // (volume.SlabSegmenter) needs the scores on the host anyway -- the global connected components run there -- so it exports
 // the graphs (bsmi_rag_graph_u8) and calls this for all blocks of a slab at once, blocks side by side on host threads.
 //
-// Algorithm: exactly rag_merge_body / agg_contract / rag_scores_kernel of seg.hip (which are bit-exact to oracle/seg_ref.c):
+// Algorithm: exactly rag_merge_body / agg_contract / rag_scores_kernel of seg_graph.hip (which are bit-exact to oracle/seg_ref.c):
 // scores 1 - sum / (255 cnt) in double, rounded to float; bin queue of `nbins` FIFO bins, bin = (int)(score * (nbins - 1));
 // initial pushes in edge order; a popped edge whose endpoint merged after its last scoring is re-scored and re-queued; a
 // merge absorbs the larger rank into the smaller, folds the dearer (by STORED score) of two parallel edges into the cheaper;
@@ -221,7 +221,7 @@ void rag_merge_scores_one(uint64_t ne, const uint64_t* edges, const uint64_t* su
   // the graph is held is not.  Nodes are numbered as they appear (nothing below looks at their order); the edge lists of a node
   // are intrusive (an edge is linked once through each end); of two merging nodes the one with the shorter list is relinked.
   // Which list is walked is free, the TIE RULE between two parallel edges is not: the specification (oracle/seg_ref.c,
-  // agg_contract in seg.hip) folds the edge of the ABSORBED region (the larger fragment id) into the survivor's only when it is
+  // agg_contract in seg_graph.hip) folds the edge of the ABSORBED region (the larger fragment id) into the survivor's only when it is
   // strictly dearer; on equal stored scores the absorbed region's edge lives on, with its place in its bin.  So every node carries
   // the smallest fragment id of its region, and when the walked list belongs to the region that survives by id the comparison is
   // taken from the other side (>= instead of >).  (Round 3 compared one way whichever list it walked: with tied scores -- u8

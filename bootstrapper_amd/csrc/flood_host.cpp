@@ -1,7 +1,7 @@
 // The 3-D seeded watershed flood on the host.
 //
 // fragments_in_xy = false (reference post/ws.py:98-110) floods a whole block from ONE priority queue; skimage's heap order
-// decides ties, so the loop is sequential by definition.  The device replay of it (seg.hip: ws3_flood_kernel) is one wave
+// decides ties, so the loop is sequential by definition.  The device replay of it (seg_ws3.hip: ws3_flood_kernel) is one wave
 // walking that loop at a global-memory round trip per pop: 12.8 s for a 128^3 block, where a host core takes 0.16 s
 // (tools/probe_ws3.py).  So the device computes mask, distance transform, maxima and markers (the data-parallel part), this
 // file floods, the device continues -- also in the block pipeline, whose 16 lanes made the device loop 0.8 s per block.

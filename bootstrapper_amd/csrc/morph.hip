@@ -144,6 +144,7 @@ __device__ __forceinline__ uint32_t uf_find(uint32_t* p, uint32_t i) {
 }
 
 // roots only ever point to smaller indices, so the forest has no cycle and a component's root is its smallest voxel
+// (seg_internal.h's cc_find / cc_unite are another algorithm -- int32_t parents, atomicMin -- and stay separate)
 __device__ __forceinline__ void uf_unite(uint32_t* p, uint32_t a, uint32_t b) {
   for (;;) {
     a = uf_find(p, a);

@@ -3,7 +3,7 @@
 // chunk_codec.cpp, the merge loops of agglo_host.cpp, the heap of flood_host.cpp -- are the pointer-heavy C++ that wants one:
 // they are compiled here with g++ -fsanitize=address,undefined, without the device half of the library.  This file supplies
 // the two things those sources take from the device half (the per-thread error message) and C entry points for the functions
-// that the product only reaches through seg.hip.  Test infrastructure: nothing here is part of libbsmi.so.
+// that the product only reaches through seg_graph.hip and seg_ws3.hip.  Test infrastructure: nothing here is part of libbsmi.so.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>

@@ -7,6 +7,18 @@ from .. import _lib
 from .._lib import lib, check
 
 
+def _affs3(affs_u8, contiguous=False):
+    """The argument check of every entry point that takes affinities (contiguous: it passes the tensor's own pointer on)."""
+    if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3 or (contiguous and not affs_u8.is_contiguous()):
+        raise ValueError(f"affs must be a {'contiguous ' if contiguous else ''}uint8 CUDA tensor of shape (3, D, H, W)")
+
+
+def _frags_like(frags, affs_u8, contiguous=False):
+    """... and of those that take the fragments of these affinities beside them."""
+    if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]) or (contiguous and not frags.is_contiguous()):
+        raise ValueError(f"fragments must be {'a contiguous' if contiguous else 'an'} int64 tensor of shape (D, H, W)")
+
+
 class SegEngine:
     def __init__(self, max_shape, device=0, host_flood=True):
         """host_flood: the one sequential flood of the 3-D fragments mode (fragments_in_xy = False) runs on the host and
@@ -31,8 +43,7 @@ class SegEngine:
         """affs_u8: uint8 CUDA tensor [3][D][H][W] -> (fragments int64 [D][H][W] holding the
         uint64 ids, max_id tensor int64[1][, seeds int64 [D][H][W]]); asynchronous on the current stream (except the 3-D
         mode of an engine with host_flood, which returns when the fragments are written)."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
+        _affs3(affs_u8)
         a = affs_u8.contiguous()
         shape = a.shape[1:]
         frags = torch.empty(tuple(shape), dtype=torch.int64, device=a.device)
@@ -47,10 +58,8 @@ class SegEngine:
     def agglomerate_mean(self, affs_u8, frags, thresholds):
         """-> int64 CUDA tensor [len(thresholds)][D][H][W]; asynchronous on the current stream
         (call status() to synchronise and check the workspace did not overflow)."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]):
-            raise ValueError("fragments must be an int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8)
+        _frags_like(frags, affs_u8)
         a = affs_u8.contiguous()
         f = frags.contiguous()
         thr = (C.c_float * len(thresholds))(*[float(t) for t in thresholds])
@@ -63,10 +72,8 @@ class SegEngine:
     def agglomerate_hist(self, affs_u8, frags, thresholds, quantile, init_with_max=False):
         """agglomerate_mean with OneMinus<HistogramQuantileAffinity<., quantile, ., 256, init_with_max>> as the scorer
         (reference post/watershed.py:230-243); the merge loop runs on the host: synchronises."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]):
-            raise ValueError("fragments must be an int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8)
+        _frags_like(frags, affs_u8)
         a = affs_u8.contiguous()
         f = frags.contiguous()
         thr = (C.c_float * len(thresholds))(*[float(t) for t in thresholds])
@@ -82,10 +89,8 @@ class SegEngine:
         by mean affinity, drop debris, crop to the write ROI, relabel 26-connected components in
         raster order and add `id_offset`.  `frags` is filtered in place.  -> (labels int64
         [crop_shape], num_labels int64[1]); asynchronous on the current stream."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]) or not frags.is_contiguous():
-            raise ValueError("fragments must be a contiguous int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8)
+        _frags_like(frags, affs_u8, contiguous=True)
         a = affs_u8.contiguous()
         shape = tuple(frags.shape)
         crop_shape = tuple(shape) if crop_shape is None else tuple(int(c) for c in crop_shape)
@@ -125,10 +130,8 @@ class SegEngine:
         (reference post/blockwise/waterz_agglom.py:106-170).  Synchronises.  -> (edges int64 [ne][2]
         holding the uint64 ids, scores float32 [ne] with NaN = never merged[, merges int64 [nm][2],
         merge_scores float32 [nm]]) as CUDA tensors."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]):
-            raise ValueError("fragments must be an int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8)
+        _frags_like(frags, affs_u8)
         a, f = affs_u8.contiguous(), frags.contiguous()
         cap = self._rag_cap = getattr(self, "_rag_cap", None) or max(1024, f.numel() // 4)
         dev = a.device
@@ -152,10 +155,8 @@ class SegEngine:
 
     def rag_agglomerate(self, affs_u8, frags, threshold, discretize_queue=256):
         """Epsilon agglomeration of `frags` IN PLACE (reference watershed_frags.py:158-177); asynchronous."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3 or not affs_u8.is_contiguous():
-            raise ValueError("affs must be a contiguous uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]) or not frags.is_contiguous():
-            raise ValueError("fragments must be a contiguous int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8, contiguous=True)
+        _frags_like(frags, affs_u8, contiguous=True)
         check(lib.bsmi_rag_agglomerate_u8(self._h, C.c_void_p(affs_u8.data_ptr()), C.c_void_p(frags.data_ptr()), _lib.i64x3(frags.shape),
                                           float(threshold), int(discretize_queue), self._stream()))
         return frags
@@ -173,10 +174,8 @@ class SegEngine:
                                merge_scores=None):
         """rag_merge_scores into caller-owned CUDA buffers, asynchronous on the current stream: edges int64 [cap][2],
         scores float32 [cap], counts int64 [>= 3] (edges, merges, nodes); status() reports a too small buffer."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3 or not affs_u8.is_contiguous():
-            raise ValueError("affs must be a contiguous uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]) or not frags.is_contiguous():
-            raise ValueError("fragments must be a contiguous int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8, contiguous=True)
+        _frags_like(frags, affs_u8, contiguous=True)
         if not (edges.is_contiguous() and scores.is_contiguous() and counts.is_contiguous()) or edges.shape[0] != scores.shape[0]:
             raise ValueError("edges / scores / counts must be contiguous and of one capacity")
         check(lib.bsmi_rag_merge_scores_u8(self._h, C.c_void_p(affs_u8.data_ptr()), C.c_void_p(frags.data_ptr()),
@@ -190,10 +189,8 @@ class SegEngine:
         """The block's region graph without the merge loop, into caller-owned CUDA buffers, asynchronous on the current stream:
         edges int64 [cap][2] (id pairs, ascending), sums int64 [cap], pair_counts int32 [cap], counts int64 [>= 3] (edges, 0,
         nodes); status() reports a too small buffer.  `rag_merge_scores_host` scores such graphs on the host."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3 or not affs_u8.is_contiguous():
-            raise ValueError("affs must be a contiguous uint8 CUDA tensor of shape (3, D, H, W)")
-        if frags.dtype != torch.int64 or tuple(frags.shape) != tuple(affs_u8.shape[1:]) or not frags.is_contiguous():
-            raise ValueError("fragments must be a contiguous int64 tensor of shape (D, H, W)")
+        _affs3(affs_u8, contiguous=True)
+        _frags_like(frags, affs_u8, contiguous=True)
         if (edges.dtype != torch.int64 or sums.dtype != torch.int64 or pair_counts.dtype != torch.int32 or counts.dtype != torch.int64
                 or not (edges.is_contiguous() and sums.is_contiguous() and pair_counts.is_contiguous() and counts.is_contiguous())
                 or not edges.shape[0] == sums.shape[0] == pair_counts.shape[0]):
@@ -205,8 +202,7 @@ class SegEngine:
     def cc_affs(self, affs_u8, threshold=0.5, remove_debris=0):
         """Thresholded-affinity connected components (reference post/cc.py; post/connected_components.py:77-101).
         -> (fragments int64, segmentation int64 (debris removed), count int64[1]); asynchronous."""
-        if affs_u8.dtype != torch.uint8 or not affs_u8.is_cuda or affs_u8.dim() != 4 or affs_u8.shape[0] != 3:
-            raise ValueError("affs must be a uint8 CUDA tensor of shape (3, D, H, W)")
+        _affs3(affs_u8)
         a = affs_u8.contiguous()
         shape = tuple(a.shape[1:])
         frags = torch.empty(shape, dtype=torch.int64, device=a.device)

@@ -195,7 +195,7 @@ def test_tensorboard_event_file_round_trip(tmp_path):
 
 def _numpy_region_graph(affs, frags):
     """edges (ascending id pairs), affinity sums and voxel-pair counts of the faces between different fragments: the pair
-    (p, p - 1 along axis d) counts with affs[d][p] (seg.hip agg_edges_kernel; waterz's region graph)"""
+    (p, p - 1 along axis d) counts with affs[d][p] (seg_graph.hip agg_edges_kernel; waterz's region graph)"""
     keys, vals = [], []
     for d in range(3):
         hi = [slice(None)] * 3

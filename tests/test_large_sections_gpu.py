@@ -1,5 +1,5 @@
 """Non-blockwise watershed on full-size sections: slices of 2^20 voxels and more (CREMI's 1250 x 1250) take the wide flood
-(csrc/seg.hip: ws_flood_wide_kernel), 3-D volumes of 2^23 voxels and more the wide host flood (csrc/flood_host.cpp); both
+(csrc/seg_ws.hip: ws_flood_wide_kernel), 3-D volumes of 2^23 voxels and more the wide host flood (csrc/flood_host.cpp); both
 bit-exact against the C oracle.  Needs an MI355X."""
 import os
 import subprocess

@@ -171,6 +171,21 @@ def _load():
         "bsmi_downscale_mean": (i32, [i32, vp, i32, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, i64p, vp]),
         "bsmi_rescale_sample": (i32, [i32, vp, i32, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), i32, vp, i64p, vp]),
         "bsmi_nonzero_bbox": (i32, [i32, vp, i32, i64p, i64p, vp, vp]),
+        "bsmi_synth_create": (i32, [i32, i64p, C.POINTER(p)]),
+        "bsmi_synth_destroy": (i32, [p]),
+        "bsmi_synth_dilate_points": (i32, [p, i64p, vp, i32, vp, vp, vp, vp, vp]),
+        "bsmi_synth_label_i32": (i32, [p, vp, i64p, vp, C.POINTER(C.c_uint64), vp]),
+        "bsmi_synth_expand_i32": (i32, [p, vp, i64p, i32, C.c_int32, vp, vp]),
+        "bsmi_synth_tubes_i32": (i32, [p, vp, i64p, vp, C.POINTER(C.c_uint64), vp]),
+        "bsmi_synth_gaussian_f32": (i32, [p, vp, i64p, vp, i32, vp, vp]),
+        "bsmi_synth_argmax_filter_f32": (i32, [p, vp, i64p, i32, vp, vp]),
+        "bsmi_synth_basins_f32": (i32, [p, vp, vp, vp, i64p, vp, C.POINTER(C.c_uint64), vp]),
+        "bsmi_synth_finish_i32": (i32, [p, vp, i64p, i32, i32, i32, vp, vp]),
+        "bsmi_synth_grow_boundary_i64": (i32, [i32, vp, i64p, C.c_uint64, i32, vp, vp]),
+        "bsmi_synth_merge_i64": (i32, [i32, vp, i64p, C.POINTER(C.c_int32), i32, C.c_int64, C.c_int64, vp]),
+        "bsmi_synth_stamp_i64": (i32, [i32, vp, i64p, i32, i32, i32, vp, i32, i32, C.c_int64, vp]),
+        "bsmi_synth_present_i64": (i32, [p, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32), vp]),
+        "bsmi_synth_split_i64": (i32, [p, vp, i64p, C.c_int64, i32, C.POINTER(C.c_int32), i32, C.c_int64, C.POINTER(C.c_uint64), vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

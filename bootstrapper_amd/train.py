@@ -11,12 +11,15 @@ callback -- third-party pipeline code outside the hot path.  `SampleSource` does
 location with the >= 5 % labelled-voxel rejection, Normalize + IntensityScaleShift(2, -1), then GrowBoundary,
 AddAffinities on the configured neighbourhood and BalanceLabels in one device call (`affinity_targets`).  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
-of each section in one launch each (csrc/train2d.hip).  The arithmetic of the step itself is libbsmi (csrc/train.hip).
+of each section in one launch each (csrc/train2d.hip).  `SyntheticSource` feeds the second-stage setups
+(models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
+`synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train.hip).
 """
 import ctypes as C
 import glob
 import json
 import os
+import random
 import re
 
 import numpy as np
@@ -380,6 +383,91 @@ class SampleSource:
         raise RuntimeError("no training location with at least 5 % labelled voxels found")
 
 
+class SyntheticSource:
+    """Infinite iterator of batches of the second-stage setups (models/3d_affs_from_2d_mtlsd/train.py:27-142, _from_2d_lsd,
+    _from_2d_affs, _from_3d_lsd), which read no data store: CreateLabels of `input_shape` -> CustomGrowBoundary(inputs'
+    grow_boundary, only_xy) -> ObfuscateLabels -> the inputs a first-stage net would have predicted from the obfuscated
+    labels (Add2DLSDs per section or AddLocalShapeDescriptor, AddAffinities on [0, dy, dx]; labels are 0 beyond the block:
+    gp.Pad(labels, None)) -> GrowBoundary(outputs' grow_boundary) on the clean labels, their affinities and balance weights
+    over the central `output_shape`.  All of it on the device (synth_labels.SynthEngine and the target calls above); the host
+    draws come from one random.Random(seed) stream, so one seed gives one sequence of batches, bit for bit.
+    Batch: raw (1, C, D, H, W) = the inputs concatenated in net_config["inputs"] order; gt_affs / affs_weights (K, d, h, w).
+
+    NOT built (logged by run_training): SimpleAugment, DeformAugment, ShiftAugment of the labels and the Noise / Intensity /
+    Smooth / Defect augmentations of the inputs."""
+
+    NOT_BUILT = ("SimpleAugment, DeformAugment and ShiftAugment of the labels; NoiseAugment, IntensityAugment, SmoothAugment and "
+                 "DefectAugment of the inputs")
+
+    def __init__(self, net_config, voxel_size=(1, 1, 1), device=0, seed=42):
+        from .synth_labels import anisotropy_range
+        ins = net_config.get("inputs", {})
+        keys = set(ins)
+        if not keys or not (keys <= {"2d_lsds", "2d_affs"} or keys == {"3d_lsds"}):
+            raise NotImplementedError(f"synthetic labels feed the inputs 2d_lsds / 2d_affs or 3d_lsds, not {sorted(keys)}")
+        if set(net_config["outputs"]) != {"3d_affs"}:
+            raise NotImplementedError(f"synthetic labels train a 3d_affs output, not {sorted(net_config['outputs'])}")
+        self.inputs = [(k, dict(v)) for k, v in ins.items()]
+        self.inp = tuple(int(v) for v in net_config["input_shape"])
+        self.out = tuple(int(v) for v in net_config["output_shape"])
+        self.vs = tuple(float(v) for v in voxel_size)
+        self.aniso = anisotropy_range(voxel_size)
+        out3d = net_config["outputs"]["3d_affs"]
+        self.out_nhood = [[int(v) for v in off] for off in out3d["neighborhood"][: int(out3d["dims"])]]
+        self.out_grow = int(out3d.get("grow_boundary", 0))
+        # models/3d_affs_from_2d_mtlsd/train.py:51 takes the 2d_affs input's grow_boundary, the others their only input's
+        self.in_grow = int((ins.get("2d_affs") or ins.get("2d_lsds") or ins.get("3d_lsds")).get("grow_boundary", 0))
+        for key, spec in self.inputs:
+            df = int(spec.get("downsample", 1))
+            if key != "2d_affs" and any(v % df for v in (self.inp[1:] if key == "2d_lsds" else self.inp)):
+                raise ValueError(f"input_shape {list(self.inp)} must be a multiple of the LSD downsample factor {df}")
+        self.device = int(device)
+        self.rng = random.Random(seed)
+        self.engine = None   # made by the first batch: the constructor touches no GPU
+
+    def __iter__(self):
+        return self
+
+    def _engine(self):
+        if self.engine is None:
+            from .synth_labels import SynthEngine
+            self.engine = SynthEngine((self.inp[0] * self.aniso[1], self.inp[1], self.inp[2]), self.device)
+        return self.engine
+
+    def labels(self):
+        """(clean labels after the inputs' grow_boundary, obfuscated labels): int64 CUDA of input_shape"""
+        from .synth_labels import draw_plan
+        eng = self._engine()
+        lab = eng.create_labels(draw_plan(self.rng, self.inp, self.aniso))
+        if self.in_grow > 0:
+            lab = eng.grow_boundary(lab, self.rng.getrandbits(64), self.in_grow)
+        return lab, eng.obfuscate(lab, self.rng)
+
+    def _input(self, key, spec, obf):
+        pad = torch.nn.functional.pad
+        if key == "2d_affs":
+            nhood = [[0] + [int(v) for v in off] for off in spec["neighborhood"][: int(spec["dims"])]]
+            lo = [max(0, -min(off[d] for off in nhood)) for d in (1, 2)]
+            hi = [max(0, max(off[d] for off in nhood)) for d in (1, 2)]
+            big = pad(obf, (lo[1], hi[1], lo[0], hi[0]))
+            return affinity_targets_roi(big[None].contiguous(), None, (0, lo[0], lo[1]), self.inp, nhood, 0, only_xy=True)[0][:, 0]
+        df, sig = int(spec.get("downsample", 1)), float(spec["sigma"])
+        if key == "2d_lsds":
+            c = [-(-int(-(-3.0 * sig // v)) // df) * df for v in self.vs[1:]]   # as SectionSource: 3 sigma, on the sub-sampling grid
+            big = pad(obf, (c[1], c[1], c[0], c[0]))
+            return lsd2d_targets(big.contiguous(), c, self.inp[1:], [sig, sig], self.vs[1:], df)[0]
+        c = [-(-int(-(-3.0 * sig // v)) // df) * df for v in self.vs]
+        big = pad(obf, (c[2], c[2], c[1], c[1], c[0], c[0]))
+        return lsd_targets(big.contiguous(), c, self.inp, sig, self.vs, df)[0]
+
+    def __next__(self):
+        lab, obf = self.labels()
+        raw = torch.cat([self._input(key, spec, obf) for key, spec in self.inputs], dim=0)[None].contiguous()
+        ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
+        affs, weights = affinity_targets_roi(lab[None].contiguous(), None, ctx, self.out, self.out_nhood, self.out_grow, only_xy=True)
+        return {"raw": raw, "gt_affs": affs[:, 0].contiguous(), "affs_weights": weights[:, 0].contiguous()}
+
+
 class PrefetchSource:
     """Batches produced ahead of the training thread (reference training.py:107-114: `DataLoader(dataset, num_workers=8,
     persistent_workers=True, pin_memory=True)`): a producer thread walks `source` -- Zarr chunk decoding runs in libbsmi's
@@ -471,8 +559,11 @@ def make_sample_source(config, net_config, device=0, rank=0):
     samples (with one seed for all, the averaged gradient would be the single-rank gradient computed N times)."""
     outs = net_config["outputs"]
     if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
-        raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
-                                  "the built-in sample source does not make; it feeds 2d_affs, 2d_lsd, 2d_mtlsd, 3d_affs, 3d_lsd and 3d_mtlsd")
+        if not config.get("synthetic_labels", False):
+            raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
+                                      "the built-in sample source makes only when the train config sets `synthetic_labels = true`; "
+                                      "without it it feeds 2d_affs, 2d_lsd, 2d_mtlsd, 3d_affs, 3d_lsd and 3d_mtlsd")
+        return SyntheticSource(net_config, config.get("voxel_size", (1, 1, 1)), device=device, seed=42 + int(rank))
     if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
         s = training_settings(net_config)
         return SectionSource(config["samples"], net_config["input_shape"], net_config["output_shape"], int(net_config.get("adj_slices", 1)),
@@ -517,10 +608,11 @@ def default_init(net_config, seed=42):
 
     for lvl in range(nl):
         conv_pass(f"unet.l_conv.{lvl}", input_channels(net_config) if lvl == 0 else nf * inc ** (lvl - 1), nf * inc ** lvl, ksd[lvl])
+    nf_out = int(net_config.get("num_fmaps_out") or nf)   # second-stage nets: width of the last right-side ConvPass, read by the heads
     for lvl in range(nl - 1):
-        conv_pass(f"unet.r_conv.0.{lvl}", nf * inc ** lvl + nf * inc ** (lvl + 1), nf * inc ** lvl, ksu[lvl])
+        conv_pass(f"unet.r_conv.0.{lvl}", nf * inc ** lvl + nf * inc ** (lvl + 1), nf_out if lvl == 0 else nf * inc ** lvl, ksu[lvl])
     for name, val in net_config["outputs"].items():
-        conv_pass(HEAD_OF_OUTPUT[name], nf, int(val["dims"]), [one])
+        conv_pass(HEAD_OF_OUTPUT[name], nf_out, int(val["dims"]), [one])
     return sd
 
 
@@ -563,6 +655,8 @@ def run_training(config_file, device=0, batches=None, log=print):
     if batches is None:
         log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops")
         batches = make_sample_source(config, net_config, device, rank)
+        if isinstance(batches, SyntheticSource):
+            log(f"note: synthetic labels (synthetic_labels = true); not built: {SyntheticSource.NOT_BUILT}")
         depth = int(config.get("prefetch", 4))   # an addition to the reference's train config: batches kept ready (0: inline)
         if depth > 0:
             batches = PrefetchSource(batches, depth, device)

@@ -663,6 +663,68 @@ int bsmi_rescale_sample(int device, const void *in_dev, int itemsize, const int6
 int bsmi_nonzero_bbox(int device, const void *in_dev, int itemsize, const int64_t shape[3], const int64_t origin[3],
                       int64_t *box_dev, void *stream);
 
+/* ---- synthetic labels of the second-stage setups (csrc/synth.hip; reference gp/create_labels.py,
+ * gp/custom_grow_boundary.py, gp/obfuscate_labels.py; the rules in full: DESIGN.md section 7i, tests/synth_ref.py) ----
+ * Every random scalar is drawn by the caller.  Volumes are [D][H][W]; a raster index is (z * H + y) * W + x.  The handle
+ * holds the work buffers for volumes of up to max_shape voxels (fewer than 2^31); one handle belongs to one host thread
+ * and one stream.  Calls that take a host table or hand back a count wait for the stream; the others are asynchronous.
+ *
+ * dilate_points: the generated sections of the tubes branch.  points: host int32 [n][3] (z, y, x) set to 1; per section z
+ *   a structuring bitmap (host uint32 [D][32], bit c of word r = structure[r][c]) of bitmap_sizes[z] = (rows, columns),
+ *   applied iterations[z] (0..10) times as scipy's binary_dilation does: origin at (rows / 2, columns / 2), zero outside
+ *   the section.  out_dev: int32 0 / 1.  A section whose two bit planes (2 * H * ceil(W / 32) words) exceed 64 KiB of
+ *   LDS is refused with BSMI_ERR_INVALID.
+ * label_i32: 26-connected components of equal non-zero values; ids are the raster ranks of the components' first voxels,
+ *   from 1 (skimage.measure.label's default on any input).  num_host (may be NULL): the number of components.
+ * expand_i32: exact Euclidean feature transform.  A voxel whose squared distance to the nearest non-zero voxel is at
+ *   most depth^2 takes that voxel's label -- among equidistant ones the one with the lowest raster index -- the others `fill`.
+ * tubes_i32: label -> expand(depth = D, fill = components + 1) -> label, as create_labels.py:134-158.
+ * gaussian_f32: three passes (z, y, x) of 2 * radius + 1 taps in float32 with the host weights, border `reflect`
+ *   (d c b a | a b c d | d c b a), repeated when the radius exceeds the axis.
+ * argmax_filter_f32: pos_dev[p] = raster index of the largest value in the window [-(w / 2), w - 1 - w / 2]^3 around p with
+ *   `reflect` border; among equal values the lowest raster index.  Values must not be NaN; -0 counts as +0.
+ * basins_f32: voxels ordered by (value, lower raster index wins).  A voxel's parent is its best 6-neighbour if that beats the
+ *   voxel, else pos_dev[p] if that is a voxel that beats it, else the voxel is a root; label = raster rank of its chain's
+ *   root, from 1.  mask_dev (uint8, may be NULL): voxels outside take 0 and are nobody's neighbour, window position or root.
+ * finish_i32: zero the ids divisible by 3 (drop3) and by 5 (drop5), keep every anisotropy-th section (section 0 alone when
+ *   anisotropy > D); out_dev int64 [ceil(D / anisotropy) or 1][H][W].
+ * grow_boundary_i64: CustomGrowBoundary(only_xy=True, no mask).  steps(z, label) = mix(mix(mix(seed) ^ z) ^ label) %
+ *   (max_steps + 1), mix = the 64-bit finaliser of MurmurHash3 (k ^= k >> 33; k *= 0xff51afd7ed558ccd; k ^= k >> 33;
+ *   k *= 0xc4ceb9fe1a85ec53; k ^= k >> 33).  A non-zero voxel keeps its label if every voxel of its section within L1
+ *   distance steps holds that label (positions outside the section count as equal), else it becomes 0.
+ * merge_i64: in the 1 or 2 sections given, label b becomes label a.  stamp_i64: the set bits of a bitmap placed with its
+ *   corner at (z, y, x) take `value`.  present_i64: the distinct non-zero ids, unordered, into ids_dev (int64
+ *   [capacity]) and their number into *count_host; BSMI_ERR_OVERFLOW beyond capacity or 32768 ids.
+ * split_i64: mask = labels == id; field = squared Euclidean distance to the nearest voxel outside the mask (the volume's
+ *   border is no background; 2^30 where there is none), 0 outside the mask; argmax_filter(window) and basins on the
+ *   mask; in the sections given, a mask voxel of fragment k takes k * scale.  num_host (may be NULL): the fragments. */
+typedef struct bsmi_synth bsmi_synth;
+int bsmi_synth_create(int device, const int64_t max_shape[3], bsmi_synth **out);
+int bsmi_synth_destroy(bsmi_synth *h);
+int bsmi_synth_dilate_points(bsmi_synth *h, const int64_t shape[3], const int32_t *points, int n_points, const uint32_t *bitmaps,
+                             const int32_t *bitmap_sizes, const int32_t *iterations, int32_t *out_dev, void *stream);
+int bsmi_synth_label_i32(bsmi_synth *h, const int32_t *in_dev, const int64_t shape[3], int32_t *out_dev, uint64_t *num_host, void *stream);
+int bsmi_synth_expand_i32(bsmi_synth *h, const int32_t *labels_dev, const int64_t shape[3], int depth, int32_t fill, int32_t *out_dev,
+                          void *stream);
+int bsmi_synth_tubes_i32(bsmi_synth *h, const int32_t *fg_dev, const int64_t shape[3], int32_t *out_dev, uint64_t *num_host, void *stream);
+int bsmi_synth_gaussian_f32(bsmi_synth *h, const float *in_dev, const int64_t shape[3], const float *weights, int radius, float *out_dev,
+                            void *stream);
+int bsmi_synth_argmax_filter_f32(bsmi_synth *h, const float *field_dev, const int64_t shape[3], int window, int32_t *pos_dev, void *stream);
+int bsmi_synth_basins_f32(bsmi_synth *h, const float *field_dev, const int32_t *pos_dev, const uint8_t *mask_dev, const int64_t shape[3],
+                          int32_t *out_dev, uint64_t *num_host, void *stream);
+int bsmi_synth_finish_i32(bsmi_synth *h, const int32_t *in_dev, const int64_t shape[3], int drop3, int drop5, int anisotropy, int64_t *out_dev,
+                          void *stream);
+int bsmi_synth_grow_boundary_i64(int device, const int64_t *in_dev, const int64_t shape[3], uint64_t seed, int max_steps, int64_t *out_dev,
+                                 void *stream);
+int bsmi_synth_merge_i64(int device, int64_t *labels_dev, const int64_t shape[3], const int32_t *sections, int n_sections, int64_t a, int64_t b,
+                         void *stream);
+int bsmi_synth_stamp_i64(int device, int64_t *labels_dev, const int64_t shape[3], int z, int y, int x, const uint32_t *bitmap, int bitmap_h,
+                         int bitmap_w, int64_t value, void *stream);
+int bsmi_synth_present_i64(bsmi_synth *h, const int64_t *labels_dev, uint64_t n_voxels, int64_t *ids_dev, uint32_t capacity, uint32_t *count_host,
+                           void *stream);
+int bsmi_synth_split_i64(bsmi_synth *h, int64_t *labels_dev, const int64_t shape[3], int64_t id, int window, const int32_t *sections,
+                         int n_sections, int64_t scale, uint64_t *num_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,18 @@ class ChunkCopy(C.Structure):
                 ("stride", C.c_int64 * 4), ("read_modify_write", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BatchFragArgs(C.Structure):
+    """bsmi_batch_frag_args of include/bsmi.h"""
+    _fields_ = [("affs_dev", C.c_void_p), ("frags_dev", C.c_void_p), ("max_id_dev", C.c_void_p), ("labels_dev", C.c_void_p),
+                ("num_labels_dev", C.c_void_p), ("id_offset", C.c_uint64), ("size_dev", C.c_void_p), ("sums_dev", C.c_void_p)]
+
+
+class BatchGraphArgs(C.Structure):
+    """bsmi_batch_graph_args of include/bsmi.h"""
+    _fields_ = [("affs_dev", C.c_void_p), ("frags_dev", C.c_void_p), ("edges_dev", C.c_void_p), ("sums_dev", C.c_void_p),
+                ("pair_counts_dev", C.c_void_p), ("counts_dev", C.c_void_p), ("edge_capacity", C.c_uint64)]
+
+
 CODEC_RAW, CODEC_ZLIB, CODEC_GZIP, CODEC_ZSTD, CODEC_LZ4, CODEC_BLOSC = range(6)
 BLOSC_LZ4, BLOSC_ZLIB, BLOSC_ZSTD = 1, 3, 4
 CHUNK_MISSING = 1
@@ -121,6 +133,10 @@ def _load():
         "bsmi_label_table_u64": (i32, [p, vp, i64p, C.c_int64, vp, vp, vp, vp, C.c_uint64, vp, vp]),
         "bsmi_seg_status": (i32, [p, vp]),
         "bsmi_seg_set_host_flood": (i32, [p, i32]),
+        "bsmi_seg_batch_create": (i32, [C.POINTER(p), i32, C.POINTER(p)]),
+        "bsmi_seg_batch_destroy": (i32, [p]),
+        "bsmi_seg_batch_fragments_u8": (i32, [p, i32, C.POINTER(BatchFragArgs), i64p, i32, i32, C.c_double, C.c_int64, i64p, i64p, C.c_uint64, vp]),
+        "bsmi_seg_batch_rag_graph_u8": (i32, [p, i32, C.POINTER(BatchGraphArgs), i64p, vp]),
         "bsmi_rag_graph_u8": (i32, [p, vp, vp, i64p, vp, vp, vp, C.c_uint64, vp, vp]),
         "bsmi_rag_merge_scores_host": (i32, [i32, vp, vp, vp, vp, C.c_float, i32, vp, i32]),
         "bsmi_rag_merge_scores_host_rule": (i32, [i32, vp, vp, vp, vp, C.c_float, i32, i32, vp, i32]),

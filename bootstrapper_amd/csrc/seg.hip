@@ -13,7 +13,7 @@ namespace bsmi {
 // Several buffers set to a 32-bit pattern by ONE launch.  The runtime's fill (hipMemsetAsync) is a launch per buffer and a narrow one:
 // the 33 MB sum table of the fragment filter took 0.84 ms beside the lanes' floods, the three tables together 1.7 ms of a block's
 // 22 ms chain, and every launch is host time of the one thread that queues all lanes (kernel trace of the driver's job).
-__global__ __launch_bounds__(256) void fill_list_kernel(FillList L) {
+__device__ __forceinline__ void fill_list_body(const FillList& L) {
   const size_t stride = (size_t)gridDim.x * blockDim.x, t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (int j = 0; j < L.n; ++j) {
     uint32_t* p = L.p[j];
@@ -29,9 +29,15 @@ __global__ __launch_bounds__(256) void fill_list_kernel(FillList L) {
     if (t0 < w - done) p[done + t0] = v;
   }
 }
+__global__ __launch_bounds__(256) void fill_list_kernel(FillList L) { fill_list_body(L); }
+__global__ __launch_bounds__(256) void fill_list_batch_kernel(const BatchBlock* __restrict__ tab) { fill_list_body(tab[blockIdx.y].fills); }
 void Fills::launch(hipStream_t s) const {
   const unsigned grid = (unsigned)std::min<size_t>((most + 255) / 256 + 1, 2048);
   hipLaunchKernelGGL(fill_list_kernel, dim3(grid), dim3(256), 0, s, L);
+}
+void batch_fill_launch(const BatchBlock* tab, int N, size_t most, hipStream_t s) {
+  const unsigned grid = (unsigned)std::min<size_t>((most + 255) / 256 + 1, 2048);
+  hipLaunchKernelGGL(fill_list_batch_kernel, dim3(grid, N), dim3(256), 0, s, tab);
 }
 
 template <typename T>

@@ -87,8 +87,8 @@ __device__ __forceinline__ uint32_t agg_rank(const AggWs& w, uint64_t f) {
 }
 
 template <bool HASH>
-__global__ void agg_edges_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, int D, int H,
-                                 int W, AggWs w) {
+__device__ __forceinline__ void agg_edges_body(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, int D, int H,
+                                 int W, const AggWs& w) {
   if (w.counters[3]) return;
   const size_t n = (size_t)D * H * W;
   const size_t hw = (size_t)H * W;
@@ -121,6 +121,15 @@ __global__ void agg_edges_kernel(const uint8_t* __restrict__ affs, const uint64_
       atomicAdd(&w.hcnt[slot], 1u);
     }
   }
+}
+template <bool HASH>
+__global__ void agg_edges_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, int D, int H,
+                                 int W, AggWs w) {
+  agg_edges_body<HASH>(affs, frags, D, H, W, w);
+}
+__global__ void agg_edges_batch_kernel(const BatchBlock* __restrict__ tab, int D, int H, int W) {
+  const BatchBlock& b = tab[blockIdx.y];
+  agg_edges_body<true>(b.g.affs, b.g.frags, D, H, W, b.agg);
 }
 
 __global__ void agg_compact_kernel(AggWs w) {
@@ -476,7 +485,7 @@ __global__ void agg_relabel_kernel(const uint64_t* __restrict__ frags, size_t n,
 // per-block RAG edge scoring (reference post/blockwise/waterz_agglom.py:106-170); restated in
 // oracle/seg_ref.c seg_rag_merge_scores_u8
 // ------------------------------------------------------------------------------------------
-__global__ void rag_ids_kernel(const uint64_t* __restrict__ frags, size_t n, int W, AggWs w) {
+__device__ __forceinline__ void rag_ids_body(const uint64_t* __restrict__ frags, size_t n, int W, const AggWs& w) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
     const uint64_t f = frags[p];
     if (!f) continue;
@@ -502,6 +511,11 @@ __global__ void rag_ids_kernel(const uint64_t* __restrict__ frags, size_t n, int
     }
     if (!done) atomicOr(&w.counters[3], 2u);
   }
+}
+__global__ void rag_ids_kernel(const uint64_t* __restrict__ frags, size_t n, int W, AggWs w) { rag_ids_body(frags, n, W, w); }
+__global__ void rag_ids_batch_kernel(const BatchBlock* __restrict__ tab, size_t n, int W) {
+  const BatchBlock& b = tab[blockIdx.y];
+  rag_ids_body(b.g.frags, n, W, b.agg);
 }
 
 __global__ void rag_pad_kernel(AggWs w) {
@@ -927,7 +941,7 @@ __global__ void rag_scores_kernel(AggWs w, uint64_t* __restrict__ edges, float* 
 // The region graph straight out of the edge hash table, for bsmi_rag_graph_u8: nodes carry the numbers rag_ids_kernel gave them
 // (insertion order), edges leave in table order; bsmi_rag_merge_scores_host brings them into ascending (id, id) order.  No sort
 // on the device: the two radix sorts of the ordered form are 46 of its 60 launches, and a block's task is launch-bound.
-__global__ void rag_graph_hash_out_kernel(AggWs w, uint64_t* __restrict__ edges, uint64_t* __restrict__ sums, uint32_t* __restrict__ cnts,
+__device__ __forceinline__ void rag_graph_hash_out_body(const AggWs& w, uint64_t* __restrict__ edges, uint64_t* __restrict__ sums, uint32_t* __restrict__ cnts,
                                           uint64_t cap, uint64_t* __restrict__ counts) {
   keep_overflow(w);
   if (w.counters[3]) return;
@@ -946,6 +960,12 @@ __global__ void rag_graph_hash_out_kernel(AggWs w, uint64_t* __restrict__ edges,
     sums[e] = w.hsum[sl];
     cnts[e] = w.hcnt[sl];
   }
+}
+__global__ void rag_graph_hash_out_kernel(AggWs w, uint64_t* __restrict__ edges, uint64_t* __restrict__ sums, uint32_t* __restrict__ cnts,
+                                          uint64_t cap, uint64_t* __restrict__ counts) { rag_graph_hash_out_body(w, edges, sums, cnts, cap, counts); }
+__global__ void rag_graph_hash_out_batch_kernel(const BatchBlock* __restrict__ tab) {
+  const BatchBlock& b = tab[blockIdx.y];
+  rag_graph_hash_out_body(b.agg, b.g.edges, b.g.sums, b.g.pair_counts, b.g.edge_capacity, b.g.counts);
 }
 
 // fragments -> ids of their merged clusters after rag_merge_kernel, in place (a cluster is named by its smallest id: the
@@ -987,6 +1007,16 @@ __global__ void seg_clear_kernel(AggWs w) {
     w.hsum[i] = 0;
     w.hcnt[i] = 0;
   }
+}
+
+// bsmi_rag_graph_u8 for rows 0..N-1 of the table (their `fills` launched by the caller); max_hcap: the largest edge table among them
+void batch_graph_launch(const BatchBlock* tab, int N, const int64_t shape[3], uint32_t max_hcap, hipStream_t s) {
+  const size_t n = (size_t)shape[0] * shape[1] * shape[2];
+  const int bs = 256;
+  const dim3 grid((unsigned)std::min<size_t>((n + bs - 1) / bs, 4096), N);
+  hipLaunchKernelGGL(rag_ids_batch_kernel, grid, dim3(bs), 0, s, tab, n, (int)shape[2]);
+  hipLaunchKernelGGL(agg_edges_batch_kernel, grid, dim3(bs), 0, s, tab, (int)shape[0], (int)shape[1], (int)shape[2]);
+  hipLaunchKernelGGL(rag_graph_hash_out_batch_kernel, dim3(std::min<uint32_t>(max_hcap / bs, 2048u), N), dim3(bs), 0, s, tab);
 }
 
 int seg_scan_grid() {

@@ -16,12 +16,14 @@
 //
 // This header is what the translation units of the engine share: the workspace handle and its parts, a few device helpers,
 // and the host launchers one file exports to another.  A kernel lives in the file that launches it:
-//   seg.hip         the handle (create / destroy / status), the batch fill, the host-side connected components
+//   seg.hip         the handle (create / destroy / status), the fill of several buffers by one launch, the host-side connected components
 //   seg_ws.hip      fragments, xy mode: seeds, offsets, the compact / plain / wide floods; the public fragments entry
 //   seg_ws3.hip     fragments, 3-D mode: EDT, max filter, markers, the single-wave flood and the hand-off to flood_host.cpp
 //   seg_graph.hip   agg_* (mean / histogram agglomeration) and rag_* (blockwise edge scoring) and their entry points
 //   seg_labels.hip  LUT relabel, fragment clean-up, the connected-components family, label statistics, the label table
 //   seg_sort.hip    the radix sorts (the only file that includes hipcub)
+//   seg_batch.hip   the batch object: a table of workspaces in device memory and the two entry points that serve every block
+//                   of a stage with one launch per kernel (the kernels' batched forms sit beside their single-block forms)
 #pragma once
 #include <vector>
 
@@ -169,6 +171,35 @@ struct Fills {
   void launch(hipStream_t s) const;
 };
 
+// ---- batched calls (seg_batch.hip): N blocks of one read shape per launch -------------------------------------------------
+// A kernel's body is a __device__ function with the single-block kernel's arguments; the batched __global__ takes them from
+// table[blockIdx.y] and calls the same body, so a block's arithmetic is the single-block form's by construction.
+constexpr int kMaxBatch = 32;
+// per-call arguments of one block (include/bsmi.h: bsmi_batch_frag_args / bsmi_batch_graph_args, the same layout)
+struct BatchFragArgs {
+  const uint8_t* affs; uint64_t* frags; uint64_t* max_id; uint64_t* labels; uint64_t* num; uint64_t id_offset;
+  uint64_t* size; uint64_t* sums;
+};
+struct BatchGraphArgs {
+  const uint8_t* affs; const uint64_t* frags; uint64_t* edges; uint64_t* sums; uint32_t* pair_counts; uint64_t* counts;
+  uint64_t edge_capacity;
+};
+// One row of the table: a handle's workspaces (written once, when the batch object is created) and the arguments and fill
+// lists of the call in flight (written by the call's first launch, in stream order: a call queued behind another cannot
+// overwrite what the earlier one still reads).
+struct BatchBlock {
+  WsScratch ws;  // seedlab = nullptr
+  uint64_t* flood_spill;
+  size_t flood_spill_stride;
+  int* status;
+  FragWs frag;
+  uint64_t* crop_tmp;
+  AggWs agg;
+  BatchFragArgs f;
+  BatchGraphArgs g;
+  FillList fills;
+};
+
 }  // namespace bsmi
 
 // The handle.  Every buffer is allocated once, by bsmi_seg_create, for max_shape; the entry points share them WITHOUT any
@@ -184,6 +215,9 @@ struct Fills {
 //       bsmi_rag_edge_stats                           reads agg.sslot / hsum / hcnt / counters as the last RAG call left them
 //       bsmi_seg_status                               reads agg.counters, agg.sticky (and clears it), frag.flags
 //   bsmi_label_stats, bsmi_lut_relabel(_multi) touch no buffer of the handle.
+//
+//   a batched call (bsmi_seg_batch_fragments_u8: F and C; bsmi_seg_batch_rag_graph_u8: G) uses those buffers of EVERY handle
+//   the batch object was created from, for the blocks it is given and also for none (its launches cover all rows it is told).
 //
 // Which calls must not be in flight together on one handle: any two of F and C (they share ws.par and crop_tmp, also a call
 // with itself), and any two of G (also a call with itself).  A call of G shares no device buffer with F or C.  "In flight
@@ -227,6 +261,18 @@ int check_seg_shape(bsmi_seg* h, const int64_t shape[3]);
 // seg_ws3.hip: the 3-D fragments mode (fragments_in_xy = 0) behind bsmi_ws_fragments_seeds_u8, arguments already validated
 int fragments_3d(bsmi_seg* h, const uint8_t* affs_dev, int D, int H, int W, int min_seed_distance, uint64_t* frags_dev,
                  uint64_t* max_id_dev, uint64_t* seeds_dev, hipStream_t s);
+
+// the batched launchers (arguments validated by seg_batch.hip; `tab` = device table, rows 0..N-1 in use)
+// seg.hip: every row's `fills` in one launch; `most` = 16-byte units of the largest buffer among them
+void batch_fill_launch(const BatchBlock* tab, int N, size_t most, hipStream_t s);
+// seg_ws.hip: is (H, W) on the LDS / compact path (the only one the batch serves)?  -> the seed kernel's LDS bytes, 0 = no
+size_t batch_ws_lds_bytes(int H, int W);
+int batch_ws_launch(const BatchBlock* tab, int N, int D, int H, int W, int msd, hipStream_t s);
+// seg_labels.hip: clean-up, crop, 26-connected relabel, label statistics
+void batch_post_launch(const BatchBlock* tab, int N, const int64_t shape[3], double filter_value, int64_t min_size, const int64_t crop_offset[3],
+                       const int64_t crop_shape[3], uint64_t stats_num, hipStream_t s);
+// seg_graph.hip: ids, edges, the graph out of the hash table
+void batch_graph_launch(const BatchBlock* tab, int N, const int64_t shape[3], uint32_t max_hcap, hipStream_t s);
 
 // seg_labels.hip: raster-order ranks of the union-find roots in f.par (cc26_count / cc26_scan / cc26_rank), their number
 // to *num_out

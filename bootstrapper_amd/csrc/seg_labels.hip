@@ -64,7 +64,7 @@ __global__ void lut_relabel_multi_kernel(const uint64_t* __restrict__ in, size_t
 // ------------------------------------------------------------------------------------------
 // blockwise fragment post-processing (reference post/blockwise/watershed_frags.py:148-156,181-224)
 // ------------------------------------------------------------------------------------------
-__global__ void frag_stats_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, FragWs w) {
+__device__ __forceinline__ void frag_stats_body(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, const FragWs& w) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
     const uint64_t f = frags[p];
     if (!f) continue;
@@ -73,6 +73,11 @@ __global__ void frag_stats_kernel(const uint8_t* __restrict__ affs, const uint64
     atomicAdd(&w.lcnt[f], 1u);
   }
 }
+__global__ void frag_stats_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, FragWs w) { frag_stats_body(affs, frags, n, w); }
+__global__ void frag_stats_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  frag_stats_body(b.f.affs, b.f.frags, n, b.frag);
+}
 
 // filter_avg_fragments: mean of the 3-channel average affinity (u8 / 255) below filter_value;
 // remove_small_objects: fewer than min_size voxels.  Both decided per fragment on the read ROI
@@ -80,7 +85,7 @@ __global__ void frag_stats_kernel(const uint8_t* __restrict__ affs, const uint64
 // ((a0/255 + a1/255) + a2/255) / 3 in raster order (numpy mean over axis 0, scipy.ndimage.mean =
 // bincount); the exact rational S / (765 n) decides unless it lies within 1e-9 of the filter,
 // where the float64 accumulation is replayed sequentially so that the outcome is the reference's.
-__global__ void frag_decide_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, FragWs w,
+__device__ __forceinline__ void frag_decide_body(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, const FragWs& w,
                                    double filter_value, long long min_size) {
   for (uint32_t f = blockIdx.x * blockDim.x + threadIdx.x; f < w.id_cap; f += gridDim.x * blockDim.x) {
     const uint32_t c = w.lcnt[f];
@@ -101,16 +106,27 @@ __global__ void frag_decide_kernel(const uint8_t* __restrict__ affs, const uint6
     if (drop) w.lcnt[f] = c | 0x80000000u;
   }
 }
+__global__ void frag_decide_kernel(const uint8_t* __restrict__ affs, const uint64_t* __restrict__ frags, size_t n, FragWs w,
+                                   double filter_value, long long min_size) { frag_decide_body(affs, frags, n, w, filter_value, min_size); }
+__global__ void frag_decide_batch_kernel(const BatchBlock* __restrict__ tab, size_t n, double filter_value, long long min_size) {
+  const BatchBlock& b = tab[blockIdx.y];
+  frag_decide_body(b.f.affs, b.f.frags, n, b.frag, filter_value, min_size);
+}
 
-__global__ void frag_filter_kernel(uint64_t* __restrict__ frags, size_t n, FragWs w) {
+__device__ __forceinline__ void frag_filter_body(uint64_t* __restrict__ frags, size_t n, const FragWs& w) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
     const uint64_t f = frags[p];
     if (!f || f >= w.id_cap) continue;
     if (w.lcnt[f] & 0x80000000u) frags[p] = 0;
   }
 }
+__global__ void frag_filter_kernel(uint64_t* __restrict__ frags, size_t n, FragWs w) { frag_filter_body(frags, n, w); }
+__global__ void frag_filter_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  frag_filter_body(b.f.frags, n, b.frag);
+}
 
-__global__ void crop_u64_kernel(const uint64_t* __restrict__ in, int H, int W, int oz, int oy, int ox, int cd, int ch,
+__device__ __forceinline__ void crop_u64_body(const uint64_t* __restrict__ in, int H, int W, int oz, int oy, int ox, int cd, int ch,
                                 int cw, uint64_t* __restrict__ out) {
   const size_t n = (size_t)cd * ch * cw;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -120,14 +136,25 @@ __global__ void crop_u64_kernel(const uint64_t* __restrict__ in, int H, int W, i
     out[i] = in[((size_t)(z + oz) * H + (y + oy)) * W + (x + ox)];
   }
 }
+__global__ void crop_u64_kernel(const uint64_t* __restrict__ in, int H, int W, int oz, int oy, int ox, int cd, int ch,
+                                int cw, uint64_t* __restrict__ out) { crop_u64_body(in, H, W, oz, oy, ox, cd, ch, cw, out); }
+__global__ void crop_u64_batch_kernel(const BatchBlock* __restrict__ tab, int H, int W, int oz, int oy, int ox, int cd, int ch, int cw) {
+  const BatchBlock& b = tab[blockIdx.y];
+  crop_u64_body(b.f.frags, H, W, oz, oy, ox, cd, ch, cw, b.crop_tmp);
+}
 
-__global__ void cc26_init_kernel(const uint64_t* __restrict__ x, size_t n, FragWs w) {
+__device__ __forceinline__ void cc26_init_body(const uint64_t* __restrict__ x, size_t n, const FragWs& w) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x)
     w.par[p] = x[p] ? (int32_t)p : -1;
 }
+__global__ void cc26_init_kernel(const uint64_t* __restrict__ x, size_t n, FragWs w) { cc26_init_body(x, n, w); }
+__global__ void cc26_init_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_init_body(b.crop_tmp, n, b.frag);
+}
 
 // unite every voxel with its 13 raster-preceding neighbours of equal value (26-connectivity)
-__global__ void cc26_union_kernel(const uint64_t* __restrict__ x, int D, int H, int W, FragWs w) {
+__device__ __forceinline__ void cc26_union_body(const uint64_t* __restrict__ x, int D, int H, int W, const FragWs& w) {
   const size_t n = (size_t)D * H * W;
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
     const uint64_t v = x[p];
@@ -147,9 +174,14 @@ __global__ void cc26_union_kernel(const uint64_t* __restrict__ x, int D, int H, 
         }
   }
 }
+__global__ void cc26_union_kernel(const uint64_t* __restrict__ x, int D, int H, int W, FragWs w) { cc26_union_body(x, D, H, W, w); }
+__global__ void cc26_union_batch_kernel(const BatchBlock* __restrict__ tab, int D, int H, int W) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_union_body(b.crop_tmp, D, H, W, b.frag);
+}
 
 // roots per 1024-voxel block (raster order), then one workgroup scans the block counts
-__global__ __launch_bounds__(1024) void cc26_count_kernel(size_t n, FragWs w) {
+__device__ __forceinline__ void cc26_count_body(size_t n, const FragWs& w) {
   __shared__ uint32_t cnt;
   if (threadIdx.x == 0) cnt = 0;
   __syncthreads();
@@ -158,8 +190,13 @@ __global__ __launch_bounds__(1024) void cc26_count_kernel(size_t n, FragWs w) {
   __syncthreads();
   if (threadIdx.x == 0) w.blk[blockIdx.x] = cnt;
 }
+__global__ __launch_bounds__(1024) void cc26_count_kernel(size_t n, FragWs w) { cc26_count_body(n, w); }
+__global__ __launch_bounds__(1024) void cc26_count_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_count_body(n, b.frag);
+}
 
-__global__ __launch_bounds__(1024) void cc26_scan_kernel(uint32_t nblk, FragWs w, uint64_t* num_out) {
+__device__ __forceinline__ void cc26_scan_body(uint32_t nblk, const FragWs& w, uint64_t* num_out) {
   __shared__ uint32_t sh[1024];
   const uint32_t chunk = (nblk + 1023) / 1024;
   const uint32_t c0 = threadIdx.x * chunk, c1 = min(nblk, c0 + chunk);
@@ -176,9 +213,14 @@ __global__ __launch_bounds__(1024) void cc26_scan_kernel(uint32_t nblk, FragWs w
   uint32_t acc = sh[threadIdx.x];
   for (uint32_t i = c0; i < c1; ++i) { const uint32_t c = w.blk[i]; w.blk[i] = acc; acc += c; }
 }
+__global__ __launch_bounds__(1024) void cc26_scan_kernel(uint32_t nblk, FragWs w, uint64_t* num_out) { cc26_scan_body(nblk, w, num_out); }
+__global__ __launch_bounds__(1024) void cc26_scan_batch_kernel(const BatchBlock* __restrict__ tab, uint32_t nblk) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_scan_body(nblk, b.frag, b.f.num);
+}
 
 // rank of every root = number of roots before it in raster order (+1)
-__global__ __launch_bounds__(1024) void cc26_rank_kernel(size_t n, FragWs w) {
+__device__ __forceinline__ void cc26_rank_body(size_t n, const FragWs& w) {
   __shared__ uint32_t sh[1024];
   const size_t p = (size_t)blockIdx.x * 1024 + threadIdx.x;
   const uint32_t flag = (p < n && w.par[p] == (int32_t)p) ? 1u : 0u;
@@ -192,6 +234,11 @@ __global__ __launch_bounds__(1024) void cc26_rank_kernel(size_t n, FragWs w) {
   }
   if (flag) w.rank[p] = (int32_t)(w.blk[blockIdx.x] + sh[threadIdx.x]);
 }
+__global__ __launch_bounds__(1024) void cc26_rank_kernel(size_t n, FragWs w) { cc26_rank_body(n, w); }
+__global__ __launch_bounds__(1024) void cc26_rank_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_rank_body(n, b.frag);
+}
 
 void cc_rank_roots(size_t n, const FragWs& f, uint64_t* num_out, hipStream_t s) {
   const uint32_t nblk = (uint32_t)((n + 1023) / 1024);
@@ -200,11 +247,16 @@ void cc_rank_roots(size_t n, const FragWs& f, uint64_t* num_out, hipStream_t s) 
   hipLaunchKernelGGL(cc26_rank_kernel, dim3(nblk), dim3(1024), 0, s, n, f);
 }
 
-__global__ void cc26_write_kernel(const uint64_t* __restrict__ x, size_t n, FragWs w, uint64_t id_offset, uint64_t* __restrict__ out) {
+__device__ __forceinline__ void cc26_write_body(const uint64_t* __restrict__ x, size_t n, const FragWs& w, uint64_t id_offset, uint64_t* __restrict__ out) {
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
     if (!x[p]) { out[p] = 0; continue; }
     out[p] = id_offset + (uint64_t)w.rank[cc_find(w.par, (int)p)];
   }
+}
+__global__ void cc26_write_kernel(const uint64_t* __restrict__ x, size_t n, FragWs w, uint64_t id_offset, uint64_t* __restrict__ out) { cc26_write_body(x, n, w, id_offset, out); }
+__global__ void cc26_write_batch_kernel(const BatchBlock* __restrict__ tab, size_t n) {
+  const BatchBlock& b = tab[blockIdx.y];
+  cc26_write_body(b.crop_tmp, n, b.frag, b.f.id_offset, b.f.labels);
 }
 
 // thresholded-affinity connected components (reference post/cc.py:7-74): voxel p is linked with p + e_d when
@@ -323,7 +375,7 @@ __global__ void ltab_gather_kernel(AggWs w, uint64_t* __restrict__ ids, uint64_t
 }
 
 // per-label voxel count and coordinate sums (RAG node attributes, watershed_frags.py:230-246)
-__global__ void label_stats_kernel(const uint64_t* __restrict__ lab, int D, int H, int W, uint64_t id_offset, uint64_t num,
+__device__ __forceinline__ void label_stats_body(const uint64_t* __restrict__ lab, int D, int H, int W, uint64_t id_offset, uint64_t num,
                                    unsigned long long* __restrict__ size, unsigned long long* __restrict__ sums) {
   const size_t n = (size_t)D * H * W;
   for (size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (size_t)gridDim.x * blockDim.x) {
@@ -335,6 +387,39 @@ __global__ void label_stats_kernel(const uint64_t* __restrict__ lab, int D, int 
     atomicAdd(&sums[3 * k + 1], (unsigned long long)((p / W) % H));
     atomicAdd(&sums[3 * k + 2], (unsigned long long)(p % W));
   }
+}
+__global__ void label_stats_kernel(const uint64_t* __restrict__ lab, int D, int H, int W, uint64_t id_offset, uint64_t num,
+                                   unsigned long long* __restrict__ size, unsigned long long* __restrict__ sums) { label_stats_body(lab, D, H, W, id_offset, num, size, sums); }
+__global__ void label_stats_batch_kernel(const BatchBlock* __restrict__ tab, int D, int H, int W, uint64_t num) {
+  const BatchBlock& b = tab[blockIdx.y];
+  label_stats_body(b.f.labels, D, H, W, b.f.id_offset, num, (unsigned long long*)b.f.size, (unsigned long long*)b.f.sums);
+}
+
+// bsmi_frag_postprocess_u8 and bsmi_label_stats (below) for rows 0..N-1 of the table, one launch per kernel.  The fills of both
+// (flags, the filter's tables, the statistics' outputs) are the rows' `fills`: the caller has launched them.
+void batch_post_launch(const BatchBlock* tab, int N, const int64_t shape[3], double filter_value, int64_t min_size, const int64_t crop_offset[3],
+                       const int64_t crop_shape[3], uint64_t stats_num, hipStream_t s) {
+  const size_t n = (size_t)shape[0] * shape[1] * shape[2];
+  const size_t nc = (size_t)crop_shape[0] * crop_shape[1] * crop_shape[2];
+  const int bs = 256;
+  const dim3 grid((unsigned)std::min<size_t>((n + bs - 1) / bs, 4096), N);
+  const dim3 gridc((unsigned)std::min<size_t>((nc + bs - 1) / bs, 4096), N);
+  if (filter_value > 0.0 || min_size > 0) {
+    hipLaunchKernelGGL(frag_stats_batch_kernel, grid, dim3(bs), 0, s, tab, n);
+    hipLaunchKernelGGL(frag_decide_batch_kernel, grid, dim3(bs), 0, s, tab, n, filter_value, (long long)min_size);
+    hipLaunchKernelGGL(frag_filter_batch_kernel, grid, dim3(bs), 0, s, tab, n);
+  }
+  const int cd = (int)crop_shape[0], ch = (int)crop_shape[1], cw = (int)crop_shape[2];
+  hipLaunchKernelGGL(crop_u64_batch_kernel, gridc, dim3(bs), 0, s, tab, (int)shape[1], (int)shape[2], (int)crop_offset[0], (int)crop_offset[1],
+                     (int)crop_offset[2], cd, ch, cw);
+  hipLaunchKernelGGL(cc26_init_batch_kernel, gridc, dim3(bs), 0, s, tab, nc);
+  hipLaunchKernelGGL(cc26_union_batch_kernel, gridc, dim3(bs), 0, s, tab, cd, ch, cw);
+  const uint32_t nblk = (uint32_t)((nc + 1023) / 1024);
+  hipLaunchKernelGGL(cc26_count_batch_kernel, dim3(nblk, N), dim3(1024), 0, s, tab, nc);
+  hipLaunchKernelGGL(cc26_scan_batch_kernel, dim3(1, N), dim3(1024), 0, s, tab, nblk);
+  hipLaunchKernelGGL(cc26_rank_batch_kernel, dim3(nblk, N), dim3(1024), 0, s, tab, nc);
+  hipLaunchKernelGGL(cc26_write_batch_kernel, gridc, dim3(bs), 0, s, tab, nc);
+  hipLaunchKernelGGL(label_stats_batch_kernel, gridc, dim3(bs), 0, s, tab, cd, ch, cw, stats_num);
 }
 
 }  // namespace bsmi

@@ -22,8 +22,8 @@ constexpr int FLOOD_LDS_HEAP = 1024; // heap entries per slice kept in LDS (8 B 
 // (int32) of the slice live in LDS ([H][W+2] uint16 + [H*W] int32, <= 160 KiB for slices up to
 // 160 x 160); LDS = false: same algorithm on the global scratch arrays (any slice size).
 template <bool LDS>
-__global__ __launch_bounds__(WS_T) void ws_seeds_kernel(const uint8_t* __restrict__ affs, int D, int H, int W,
-                                                        int msd, WsScratch s, int compact) {
+__device__ __forceinline__ void ws_seeds_body(const uint8_t* __restrict__ affs, int D, int H, int W, int msd, const WsScratch& s,
+                                              int compact) {
   extern __shared__ __attribute__((aligned(16))) char ws_smem[];
   const int z = blockIdx.x;
   const int n = H * W;
@@ -330,13 +330,28 @@ __global__ __launch_bounds__(WS_T) void ws_seeds_kernel(const uint8_t* __restric
     else lab[i] = l;
   }
 }
+template <bool LDS>
+__global__ __launch_bounds__(WS_T) void ws_seeds_kernel(const uint8_t* __restrict__ affs, int D, int H, int W,
+                                                        int msd, WsScratch s, int compact) {
+  ws_seeds_body<LDS>(affs, D, H, W, msd, s, compact);
+}
+// batched form (LDS / compact path): block blockIdx.y of the table, slice blockIdx.x
+__global__ __launch_bounds__(WS_T) void ws_seeds_batch_kernel(const BatchBlock* __restrict__ tab, int D, int H, int W, int msd, int compact) {
+  const BatchBlock& b = tab[blockIdx.y];
+  ws_seeds_body<true>(b.f.affs, D, H, W, msd, b.ws, compact);
+}
 
-__global__ void ws_offsets_kernel(int D, WsScratch s, uint64_t* max_id) {
+__device__ __forceinline__ void ws_offsets_body(int D, const WsScratch& s, uint64_t* max_id) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     uint64_t acc = 0;
     for (int z = 0; z < D; ++z) { s.offs[z] = acc; acc += (uint64_t)s.nseeds[z]; }
     *max_id = acc;
   }
+}
+__global__ void ws_offsets_kernel(int D, WsScratch s, uint64_t* max_id) { ws_offsets_body(D, s, max_id); }
+__global__ void ws_offsets_batch_kernel(const BatchBlock* __restrict__ tab, int D) {
+  const BatchBlock& b = tab[blockIdx.y];
+  ws_offsets_body(D, b.ws, b.f.max_id);
 }
 
 // lane 0's 64-bit value to the whole wave
@@ -357,8 +372,8 @@ __device__ __forceinline__ bool flood_smaller(uint64_t a, uint64_t b) { return (
 // instead of 230 -- side by side, the floods of a stage's blocks are bound by the lines they pull through L2, not by one wave's
 // latency chain.
 template <bool COMPACT>
-__global__ __launch_bounds__(64 * FLOOD_WAVES) void ws_flood_kernel(int D, int H, int W, WsScratch s, uint64_t* heap_spill,
-                                                     size_t spill_stride, uint64_t* __restrict__ frags, int* status) {
+__device__ __forceinline__ void ws_flood_body(int D, int H, int W, const WsScratch& s, uint64_t* heap_spill, size_t spill_stride,
+                                              uint64_t* __restrict__ frags, int* status) {
   __shared__ uint64_t hl_all[FLOOD_WAVES][FLOOD_LDS_HEAP];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -575,6 +590,16 @@ __global__ __launch_bounds__(64 * FLOOD_WAVES) void ws_flood_kernel(int D, int H
     out[i] = l ? (uint64_t)l + off : 0ull;
   }
   (void)status;
+}
+template <bool COMPACT>
+__global__ __launch_bounds__(64 * FLOOD_WAVES) void ws_flood_kernel(int D, int H, int W, WsScratch s, uint64_t* heap_spill,
+                                                     size_t spill_stride, uint64_t* __restrict__ frags, int* status) {
+  ws_flood_body<COMPACT>(D, H, W, s, heap_spill, spill_stride, frags, status);
+}
+// batched form (compact record): block blockIdx.y of the table, slices blockIdx.x * FLOOD_WAVES ... of it
+__global__ __launch_bounds__(64 * FLOOD_WAVES) void ws_flood_batch_kernel(const BatchBlock* __restrict__ tab, int D, int H, int W) {
+  const BatchBlock& b = tab[blockIdx.y];
+  ws_flood_body<true>(D, H, W, b.ws, b.flood_spill, b.flood_spill_stride, b.f.frags, b.status);
 }
 
 // The flood of slices of 2^20 voxels and more (up to 4096 x 4096): ws_flood_kernel's packed entry has 20 bits for the age and
@@ -821,6 +846,43 @@ __global__ void ws_seeds_out_kernel(int D, size_t n, WsScratch s, uint64_t* __re
 
 using namespace bsmi;
 
+static size_t ws_seeds_lds_bytes(int H, int W) {
+  const size_t hw16 = ((size_t)H * W + 15) & ~(size_t)15;
+  return (((size_t)H * (W + 2) * 2 + 15) & ~(size_t)15) + (((size_t)H * W * 2 + 15) & ~(size_t)15) + 2 * hw16;
+}
+static bool ws_seeds_use_lds(int H, int W) {
+  return ws_seeds_lds_bytes(H, W) <= 158 * 1024 && (size_t)H * H + (size_t)W * W < 65535 && (H + 1) * (H + 1) + W * W < 65535;
+}
+static bool flood_compact_ok() {
+  static const bool ok = [] { const char* e = getenv("BSMI_FLOOD_COMPACT"); return !(e && e[0] == '0'); }();
+  return ok;
+}
+
+namespace bsmi {
+
+size_t batch_ws_lds_bytes(int H, int W) {
+  return ws_seeds_use_lds(H, W) && flood_compact_ok() && (size_t)H * W < ((size_t)1 << 20) ? ws_seeds_lds_bytes(H, W) : 0;
+}
+
+// Seeds of every block, then the offsets, then the floods: a seed workgroup needs a whole CU's LDS, and a CU that holds a flood
+// workgroup has none to give -- in one stream, every block's seeds are through before the first flood starts.
+int batch_ws_launch(const BatchBlock* tab, int N, int D, int H, int W, int msd, hipStream_t s) {
+  const size_t lds = batch_ws_lds_bytes(H, W);
+  if (!lds) BSMI_FAIL(BSMI_ERR_INVALID, "slices of %d x %d are off the LDS / compact path: not served in batches", H, W);
+  static DeviceOnce once;
+  const int rc_once = once.run([&]() -> int {
+    BSMI_HIP(hipFuncSetAttribute((const void*)ws_seeds_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+    return BSMI_OK;
+  });
+  if (rc_once) return rc_once;
+  hipLaunchKernelGGL(ws_seeds_batch_kernel, dim3(D, N), dim3(WS_T), lds, s, tab, D, H, W, msd, 1);
+  hipLaunchKernelGGL(ws_offsets_batch_kernel, dim3(1, N), dim3(64), 0, s, tab, D);
+  hipLaunchKernelGGL(ws_flood_batch_kernel, dim3((D + FLOOD_WAVES - 1) / FLOOD_WAVES, N), dim3(64 * FLOOD_WAVES), 0, s, tab, D, H, W);
+  return BSMI_OK;
+}
+
+}  // namespace bsmi
+
 static int fragments_xy(bsmi_seg* h, const uint8_t* affs_dev, int D, int H, int W, int min_seed_distance, uint64_t* frags_dev,
                         uint64_t* max_id_dev, uint64_t* seeds_dev, hipStream_t s) {
   // Slices of 2^20 voxels and more take ws_flood_wide_kernel, whose row index is exact for W <= 4096 and whose keys hold
@@ -844,12 +906,10 @@ static int fragments_xy(bsmi_seg* h, const uint8_t* affs_dev, int D, int H, int 
   {
     // squared distances must fit the uint16 intermediates of the LDS path: H^2 + W^2 < 65535
     // sg u16 [H][W+2] | sd2 u16 [H*W] | smask u8 [H*W] | sflag u8 [H*W], each 16-byte aligned (ws_seeds_kernel)
-    const size_t hw16 = ((size_t)H * W + 15) & ~(size_t)15;
-    const size_t lds = (((size_t)H * (W + 2) * 2 + 15) & ~(size_t)15) + (((size_t)H * W * 2 + 15) & ~(size_t)15) + 2 * hw16;
-    const bool use_lds = lds <= 158 * 1024 && (size_t)H * H + (size_t)W * W < 65535 && (H + 1) * (H + 1) + W * W < 65535;
+    const size_t lds = ws_seeds_lds_bytes(H, W);
+    const bool use_lds = ws_seeds_use_lds(H, W);
     // (then also H * W < 32768: a slice's marker labels and voxel indices fit the compact record's 16 bits)
-    static const bool compact_ok = [] { const char* e = getenv("BSMI_FLOOD_COMPACT"); return !(e && e[0] == '0'); }();
-    compact = use_lds && compact_ok;
+    compact = use_lds && flood_compact_ok();
     if (use_lds) {
       static DeviceOnce once;
       const int rc_once = once.run([&]() -> int {

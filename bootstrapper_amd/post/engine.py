@@ -236,6 +236,75 @@ class SegEngine:
         check(lib.bsmi_seg_status(self._h, self._stream()))
 
 
+class SegBatch:
+    """Several SegEngine workspaces of one device behind one launch per kernel (include/bsmi.h: bsmi_seg_batch): block i of a
+    call uses engine i.  Serves the default blockwise path only -- xy fragments on slices of the LDS path, clean-up, crop,
+    relabel, label statistics; the region graph -- and raises BsmiError(ERR_INVALID) for anything else.  Asynchronous on the
+    current stream; overflows are reported by the engines' own status()."""
+
+    def __init__(self, engines):
+        self.engines = list(engines)   # (kept alive: the batch object points into their workspaces)
+        self.device = self.engines[0].device
+        self._h = C.c_void_p()
+        hs = (C.c_void_p * len(self.engines))(*[e._h.value for e in self.engines])
+        check(lib.bsmi_seg_batch_create(hs, len(self.engines), C.byref(self._h)))
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib.bsmi_seg_batch_destroy(h)
+            self._h = None
+
+    def __len__(self):
+        return len(self.engines)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+
+    def fragments(self, affs, frags, labels, nums, id_offsets, sizes, sums, min_seed_distance=10, filter_value=0.0, min_size=0,
+                  crop_offset=(0, 0, 0), max_ids=None):
+        """Per block i: ws_fragments(affs[i]) -> frags[i]; postprocess_fragments(..., crop_offset, labels[i].shape, id_offsets[i])
+        -> labels[i], nums[i]; label_stats(labels[i], id_offsets[i], len(sizes[i])) -> sizes[i], sums[i].  Lists of contiguous
+        CUDA tensors: affs uint8 [3][D][H][W] and frags int64 [D][H][W] of ONE shape, labels int64 of one crop shape, nums int64
+        [1], sizes int64 [cap], sums int64 [cap][3]."""
+        n = len(affs)
+        shape, crop = tuple(frags[0].shape), tuple(labels[0].shape)
+        cap = int(sizes[0].numel())
+        if max_ids is None:
+            max_ids = torch.empty(n, dtype=torch.int64, device=affs[0].device)
+        args = (_lib.BatchFragArgs * n)()
+        for i in range(n):
+            _affs3(affs[i], contiguous=True)
+            _frags_like(frags[i], affs[i], contiguous=True)
+            if tuple(frags[i].shape) != shape or tuple(labels[i].shape) != crop or labels[i].dtype != torch.int64 or not labels[i].is_contiguous():
+                raise ValueError("the blocks of a batch share one shape and one crop shape (contiguous int64 labels)")
+            if (sizes[i].dtype != torch.int64 or sums[i].dtype != torch.int64 or sizes[i].numel() != cap or sums[i].numel() != 3 * cap
+                    or nums[i].dtype != torch.int64 or not (sizes[i].is_contiguous() and sums[i].is_contiguous())):
+                raise ValueError("sizes int64 [cap], sums int64 [cap][3] (contiguous, one capacity), nums int64 [1]")
+            args[i] = _lib.BatchFragArgs(affs[i].data_ptr(), frags[i].data_ptr(), max_ids[i:i + 1].data_ptr(), labels[i].data_ptr(),
+                                         nums[i].data_ptr(), int(id_offsets[i]), sizes[i].data_ptr(), sums[i].data_ptr())
+        check(lib.bsmi_seg_batch_fragments_u8(self._h, n, args, _lib.i64x3(shape), 1, int(min_seed_distance), float(filter_value),
+                                              int(min_size), _lib.i64x3(crop_offset), _lib.i64x3(crop), cap, self._stream()))
+        return max_ids
+
+    def rag_graph(self, affs, frags, edges, sums, pair_counts, counts):
+        """Per block i: SegEngine.rag_graph_async(affs[i], frags[i], edges[i], sums[i], pair_counts[i], counts[i])."""
+        n = len(affs)
+        shape = tuple(frags[0].shape)
+        args = (_lib.BatchGraphArgs * n)()
+        for i in range(n):
+            _affs3(affs[i], contiguous=True)
+            _frags_like(frags[i], affs[i], contiguous=True)
+            e, s, c, k = edges[i], sums[i], pair_counts[i], counts[i]
+            if (tuple(frags[i].shape) != shape or e.dtype != torch.int64 or s.dtype != torch.int64 or c.dtype != torch.int32 or k.dtype != torch.int64
+                    or not (e.is_contiguous() and s.is_contiguous() and c.is_contiguous() and k.is_contiguous())
+                    or not e.shape[0] == s.shape[0] == c.shape[0] or k.numel() < 3):
+                raise ValueError("one shape; edges int64 [cap][2], sums int64 [cap], pair_counts int32 [cap], counts int64 [>= 3]: contiguous, one capacity")
+            args[i] = _lib.BatchGraphArgs(affs[i].data_ptr(), frags[i].data_ptr(), e.data_ptr(), s.data_ptr(), c.data_ptr(), k.data_ptr(),
+                                          int(e.shape[0]))
+        check(lib.bsmi_seg_batch_rag_graph_u8(self._h, n, args, _lib.i64x3(shape), self._stream()))
+
+
 QUEUE_BINS_FORMULAS = {"n_minus_1": 0, "n": 1}   # include/bsmi.h BSMI_QUEUE_BINS_*
 
 

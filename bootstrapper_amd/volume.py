@@ -279,6 +279,21 @@ class SlabSegmenter:
         # readers' copy streams, the lanes): without this wait a fill could land on top of data (found with the streamed driver,
         # whose third pass read affinities into a slab whose memset had not run yet: an all-zero block layer)
         torch.cuda.current_stream(self.dev).synchronize()
+        # Stage-by-stage runs serve the blocks of a stage in batches: one launch per kernel for up to len(lanes) blocks of one
+        # read shape (post/engine.py SegBatch over the lanes' workspaces), so that the stage's concurrency is the grid's and not
+        # the number of hardware queues the runtime grants the lanes' streams (HIP's default: 4).  BSMI_SEG_BATCH=0: the lanes.
+        # BSMI_SEG_BATCH_STREAMS=S: the workspaces dealt to S batch objects with a stream each (batches of len(lanes) / S blocks).
+        self._batchers = []
+        self._lane_events = []
+        if (os.environ.get("BSMI_SEG_BATCH", "1") != "0" and self.host_scores and self.fragments_in_xy and self.epsilon == 0
+                and all(v is None for v in self.shift.values())):
+            from .post.engine import SegBatch
+            S = max(1, min(int(os.environ.get("BSMI_SEG_BATCH_STREAMS", "1")), len(self.lanes)))
+            for g in range(S):
+                mine = self.lanes[g::S][:32]
+                self._batchers.append(dict(batch=SegBatch([lane["engine"] for lane in mine]), lanes=mine, stream=mine[0]["stream"],
+                                           max_ids=torch.zeros(len(mine), dtype=torch.int64, device=self.dev)))
+            torch.cuda.current_stream(self.dev).synchronize()
         self.nodes = None
         self.rag_edges = self.rag_scores = None
         self.luts = None
@@ -444,6 +459,79 @@ class SlabSegmenter:
             else:
                 lane["engine"].rag_merge_scores_async(a, f, 1.0, self.bins, self.edges[k], self.scores[k], self.counts_dev[k])
 
+    def _batch_stage(self, kind, ks, wait=()):
+        """Blocks `ks` of stage `kind` ("f": fragments, clean-up, relabel, node statistics; "s": region graphs) in batches: per
+        read shape, up to a batcher's number of workspaces per batch, the batches dealt to the batchers in turn.  -> the blocks
+        of the shapes the library does not serve in batches (ERR_INVALID, nothing launched for them): the lanes' to do."""
+        groups = {}
+        for k in ks:
+            groups.setdefault(tuple(sl.stop - sl.start for sl in self._read_slices(k)), []).append(k)
+        pending, self._lane_events = list(wait) + self._lane_events, []
+        waited = set()
+        refused, turn = [], 0
+        for rshape, group in groups.items():
+            wshape = tuple(r - 2 * c for r, c in zip(rshape, self.ctx))
+            i = 0
+            while i < len(group):
+                bt = self._batchers[turn % len(self._batchers)]
+                chunk = group[i:i + len(bt["lanes"])]
+                st = bt["stream"]
+                with torch.cuda.stream(st):
+                    if id(bt) not in waited:
+                        waited.add(id(bt))
+                        for ev in pending:
+                            st.wait_event(ev)
+                    A, F, L = [], [], []
+                    for lane, k in zip(bt["lanes"], chunk):
+                        a = self._buf(lane["a"], rshape, (3,))
+                        a.copy_(self.affs[(slice(None),) + self._read_slices(k)])
+                        f = self._buf(lane["f"], rshape)
+                        if kind == "s":
+                            f.copy_(self.frags[self._read_slices(k)])
+                        A.append(a)
+                        F.append(f)
+                        L.append(self._buf(lane["lab"], wshape))
+                    try:
+                        if kind == "f":
+                            bt["batch"].fragments(A, F, L, [self.nums[k:k + 1] for k in chunk], [self.block_ids[k] * self.nvb for k in chunk],
+                                                  [self.sizes[k] for k in chunk], [self.sums[k] for k in chunk], self.msd, self.filter_fragments,
+                                                  self.remove_debris, self.ctx, max_ids=bt["max_ids"])
+                        else:
+                            bt["batch"].rag_graph(A, F, [self.edges[k] for k in chunk], [self.esums[k] for k in chunk],
+                                                  [self.scores[k].view(torch.int32) for k in chunk], [self.counts_dev[k] for k in chunk])
+                    except _lib.BsmiError as exc:
+                        if exc.code != _lib.ERR_INVALID:
+                            raise
+                        refused.extend(group[i:])
+                        break
+                    if kind == "f":
+                        for k, lab in zip(chunk, L):
+                            b, e = self.boxes[k]
+                            self.frags[tuple(slice(c + lo, c + hi) for c, lo, hi in zip(self.ctx, b, e))].copy_(lab)
+                        done = torch.cuda.Event()
+                        done.record(st)
+                        for k in chunk:
+                            self.frag_done[k] = done
+                i += len(chunk)
+                turn += 1
+        return refused
+
+    def _lanes_stage(self, kind, ks, wait=()):
+        """Blocks `ks` of a stage on the lanes, within a run that also batches: behind what the batchers have queued so far (a
+        batch uses every lane's workspace and buffers), and the next batches behind them (`_lane_events`)."""
+        if not ks:
+            return
+        tails = []
+        for bt in self._batchers:
+            ev = torch.cuda.Event()
+            ev.record(bt["stream"])
+            tails.append(ev)
+        for k in ks:
+            (self._launch_fragments if kind == "f" else self._launch_scores)(k, list(wait) + tails)
+            ev = torch.cuda.Event()
+            ev.record(self.lane_of(kind, k)["stream"])
+            self._lane_events.append(ev)
+
     def _collect(self):
         """end of the two block stages: one synchronisation, overflow checks, the edges every block owns (the block that
         created the smaller-id fragment, see post/blockwise.py) to the host"""
@@ -548,7 +636,29 @@ class SlabSegmenter:
         nb = [self._neighbours(k) for k in range(K)]
         queued, scored = set(), set()
 
+        batched = bool(self._batchers) and not overlap
+        self._lane_events = []
+
+        def fragments_of(ks, wait):
+            if batched:
+                self._lanes_stage("f", self._batch_stage("f", ks, wait), wait)
+            else:
+                for k in ks:
+                    self._launch_fragments(k, wait)
+            queued.update(ks)
+
         def score_what_can_be(candidates, extra=()):
+            if batched:
+                # one stage after the other: every block scored here follows the fragments of ALL blocks queued so far
+                todo = [j for j in candidates if j not in scored and all(i in queued for i in nb[j])]
+                seen, wait = set(), list(extra)
+                for i in sorted(queued):
+                    if id(self.frag_done[i]) not in seen:
+                        seen.add(id(self.frag_done[i]))
+                        wait.append(self.frag_done[i])
+                self._lanes_stage("s", self._batch_stage("s", todo, wait), wait)
+                scored.update(todo)
+                return
             for j in candidates:
                 if j not in scored and all(i in queued for i in nb[j]):
                     self._launch_scores(j, list(extra) + [self.frag_done[i] for i in nb[j]])
@@ -572,9 +682,7 @@ class SlabSegmenter:
                 err = exc
 
         def launch_inner():
-            for k in inner:
-                self._launch_fragments(k, (ready[K - 1],))
-                queued.add(k)
+            fragments_of(inner, (ready[K - 1],))
         def launch_overlapped():
             # Host-driven: a block's stage is launched once its inputs EXIST (event queries), so no lane ever sits behind
             # a device-side wait -- parked queues are polled by the command processor at the predict stream's expense.
@@ -610,11 +718,13 @@ class SlabSegmenter:
             got = self._exchange(self.affs)
 
             def launch_face():
+                if not overlap:
+                    fragments_of(face, (got,))
+                    return
                 for k in face:
                     self._launch_fragments(k, (got,))
                     queued.add(k)
-                    if overlap:
-                        score_what_can_be([j for j in nb[k] if j in inner_set])
+                    score_what_can_be([j for j in nb[k] if j in inner_set])
             guarded(launch_face)
         guarded(lambda: score_what_can_be(inner))
         if face:
@@ -781,6 +891,20 @@ class SlabSegmenter:
             self._lane_load = [0] * len(self.lanes)
             for lane in self.lanes:
                 lane["stream"].synchronize()
+            if self._batchers:
+                # ... and the batched forms of the kernels, on every workspace: a full batch of each read shape that has one
+                # (else its blocks), both stages
+                groups = {}
+                for k in range(len(self.boxes)):
+                    groups.setdefault(tuple(sl.stop - sl.start for sl in self._read_slices(k)), []).append(k)
+                ks = [k for g in groups.values() for k in g[:len(self.lanes)]]
+                self._lane_events = []
+                self._lanes_stage("f", self._batch_stage("f", ks))
+                wait = [ev for ev in {id(self.frag_done[k]): self.frag_done[k] for k in ks}.values()]
+                self._lanes_stage("s", self._batch_stage("s", ks, wait), wait)
+                self._lane_events = []
+                for lane in self.lanes:
+                    lane["stream"].synchronize()
 
     def run(self, ready=None, overlap=False):
         if ready is not None and not overlap:

@@ -510,6 +510,45 @@ int bsmi_seg_set_host_flood(bsmi_seg *h, int on);
  * After an overflow the outputs of that call are undefined. */
 int bsmi_seg_status(bsmi_seg *h, void *stream);
 
+/* Batches: the blocks of a blockwise stage served by ONE launch per kernel instead of a chain of launches per block on a stream
+ * each (whose concurrency is the number of hardware queues the runtime grants: 4 by default).  A batch object is made from n
+ * (1..32) workspaces of one device; block i of a call uses workspace i (its F and C buffers in a fragments call, its G buffers in
+ * a graph call: see the handle's rule in csrc/seg_internal.h), so calls on one batch object belong to one stream, and no
+ * single-handle call may run on one of its workspaces meanwhile.  Overflows stay per workspace: bsmi_seg_status(handle i).
+ * The calls are asynchronous, never synchronise with the host and read no host memory after they return.
+ * Served: fragments_in_xy = 1 on slices of the LDS path (H^2 + W^2 < 65535 and the seed kernel's arrays within 158 KiB, e.g. up to
+ * 160 x 160), all n_blocks blocks of ONE shape.  Everything else returns BSMI_ERR_INVALID and is the single-handle calls' to do. */
+typedef struct bsmi_seg_batch bsmi_seg_batch;
+typedef struct {
+  const uint8_t *affs_dev;   /* [3][shape] */
+  uint64_t *frags_dev;       /* [shape]: the fragments before the crop (filtered in place), as bsmi_ws_fragments_u8 writes them */
+  uint64_t *max_id_dev;      /* [1] */
+  uint64_t *labels_dev;      /* [crop_shape]: bsmi_frag_postprocess_u8's out_dev */
+  uint64_t *num_labels_dev;  /* [1] */
+  uint64_t id_offset;
+  uint64_t *size_dev;        /* [stats_num], bsmi_label_stats of labels_dev */
+  uint64_t *sums_dev;        /* [stats_num][3] */
+} bsmi_batch_frag_args;
+typedef struct {
+  const uint8_t *affs_dev;
+  const uint64_t *frags_dev;
+  uint64_t *edges_dev;
+  uint64_t *sums_dev;
+  uint32_t *pair_counts_dev;
+  uint64_t *counts_dev;
+  uint64_t edge_capacity;
+} bsmi_batch_graph_args;
+int bsmi_seg_batch_create(bsmi_seg *const *handles, int n, bsmi_seg_batch **out);
+int bsmi_seg_batch_destroy(bsmi_seg_batch *b);  /* before the handles it was made from */
+/* per block: bsmi_ws_fragments_u8, bsmi_frag_postprocess_u8 (filter_value, min_size, crop, id_offset) and bsmi_label_stats
+ * (id_offset, stats_num) on the crop, bit for bit */
+int bsmi_seg_batch_fragments_u8(bsmi_seg_batch *b, int n_blocks, const bsmi_batch_frag_args *args, const int64_t shape[3],
+                                int fragments_in_xy, int min_seed_distance, double filter_value, int64_t min_size,
+                                const int64_t crop_offset[3], const int64_t crop_shape[3], uint64_t stats_num, void *stream);
+/* per block: bsmi_rag_graph_u8 */
+int bsmi_seg_batch_rag_graph_u8(bsmi_seg_batch *b, int n_blocks, const bsmi_batch_graph_args *args, const int64_t shape[3],
+                                void *stream);
+
 /* ---- evaluation ---- */
 /* `bs evaluate` (evaluate.py:39-101): affinity error maps of a segmentation against the network's own affinities
  * (eval/compute_errors.py:25-223, gp/add_aff_errors.py) and the (gt, seg) contingency table behind Rand / VOI

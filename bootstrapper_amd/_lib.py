@@ -43,6 +43,22 @@ class StepInfo(C.Structure):
                 ("factor", C.c_int32 * 3), ("offset", C.c_int32 * 3), ("prefix", C.c_char * 64)]
 
 
+class TrainWgradInfo(C.Structure):
+    """bsmi_unet_train_wgrad_info of include/bsmi.h"""
+    _fields_ = [(n, C.c_int32) for n in ("family", "residual", "n", "c", "cbase", "kx", "tile_n", "tile_c", "ranges", "lines_per_range",
+                                         "det_workspace")]
+
+
+class TrainStepInfo(C.Structure):
+    """bsmi_unet_train_step_info of include/bsmi.h"""
+    _fields_ = [("type", C.c_int32), ("n_wgrad", C.c_int32), ("wgrad", TrainWgradInfo * 4), ("dgrad", C.c_int32), ("dgrad_raw", C.c_int32),
+                ("dgrad_converted", C.c_int32), ("dgrad_bn", C.c_int32), ("dgrad_ksteps", C.c_int32), ("dgrad_split_k", C.c_int32),
+                ("dgrad_scatter", C.c_int32), ("dgrad_residual", C.c_int32), ("border", C.c_int32 * 3), ("has_split", C.c_int32),
+                ("bias", C.c_int32), ("up", C.c_int32), ("fwd_split", C.c_int32), ("deterministic", C.c_int32)]
+
+
+WGRAD_FAMILIES = ("none", "wave-f32", "tiled-f32", "split-bf16")
+TRAIN_TENSORS = {"dout": 0, "gmask": 1, "gsplit": 2, "gsplit_hi": 3, "gsplit_lo": 4, "dcat": 5, "head_dp": 6, "pad_count": 7}
 STEP_TYPES = ("input", "conv", "pool", "up", "head")
 CONV_FORMS = ("gather", "raster-halo", "box-halo", "halo-resident", "first-pass", "winograd F(2x2)", "winograd F(4x4)")
 STEP_FLAGS = {1: "fused-up", 2: "res-low", 4: "split-k"}
@@ -156,6 +172,8 @@ def _load():
         "bsmi_unet_train_write_param": (i32, [p, C.c_char_p, C.c_int, vp]),
         "bsmi_unet_train_step_count": (i32, [p, C.c_int, C.POINTER(C.c_int)]),
         "bsmi_unet_train_end": (i32, [p]),
+        "bsmi_unet_train_debug_tensor": (i32, [p, i32, i32, i64p, vp, C.c_uint64]),
+        "bsmi_unet_train_debug_step_info": (i32, [p, i32, C.POINTER(TrainStepInfo)]),
         "bsmi_train_affinity_targets": (i32, [C.c_int, vp, vp, i64p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_float,
                                               C.c_float, vp, vp, vp]),
         "bsmi_train_lsd_targets": (i32, [C.c_int, vp, vp, i64p, i64p, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, vp, vp, vp]),

@@ -1040,7 +1040,7 @@ static int wgrad_tile_c(int c) { return c <= 32 ? 32 : 64; }
 static int wgrad_pad(int channels, int tile) { return (channels + tile - 1) / tile * tile; }
 
 template <int KX, int FNW, int FCW>
-static int launch_wgrad_x3_t(WgradPk a, hipStream_t s) {
+static int launch_wgrad_x3_t(WgradPk a, hipStream_t s, bsmi_unet_train_wgrad_info* wi) {
   constexpr int TN = 32 * FNW, TC = 32 * FCW, XVEC = KX > 1 ? 2 : 1;
   constexpr int smem = 2 * (2 * 4 * TN * 16 + 2 * XVEC * 4 * TC * 16);
   static DeviceOnce once;
@@ -1058,19 +1058,23 @@ static int launch_wgrad_x3_t(WgradPk a, hipStream_t s) {
   a.zsplit = (nlines + a.lines_per_block - 1) / a.lines_per_block;
   if (a.zstride && a.zsplit > zcap) BSMI_FAIL(BSMI_ERR_STATE, "weight-gradient launch cut into %d line ranges, workspace for %d", a.zsplit, zcap);
   const int units = blocks_nc * a.zsplit;
+  if (wi) {  // (bsmi_unet_train_debug_step_info)
+    wi->family = BSMI_WGRAD_SPLIT; wi->kx = KX; wi->tile_n = TN; wi->tile_c = TC;
+    wi->ranges = a.zsplit; wi->lines_per_range = a.lines_per_block; wi->det_workspace = a.zstride ? 1 : 0;
+  }
   hipLaunchKernelGGL((wgrad_x3_kernel<KX, FNW, FCW>), dim3((units + 7) / 8 * 8 * trows), dim3(256), smem, s, a);
   return BSMI_OK;
 }
 
 template <int KX>
-static int launch_wgrad_x3_k(const WgradPk& a, hipStream_t s) {
+static int launch_wgrad_x3_k(const WgradPk& a, hipStream_t s, bsmi_unet_train_wgrad_info* wi) {
   const int fn = wgrad_tile_n(a.N) / 32, fc = wgrad_tile_c(a.C) / 32;
-  if (fn == 1 && fc == 1) return launch_wgrad_x3_t<KX, 1, 1>(a, s);
-  if (fn == 1 && fc == 2) return launch_wgrad_x3_t<KX, 1, 2>(a, s);
-  if (fn == 2 && fc == 1) return launch_wgrad_x3_t<KX, 2, 1>(a, s);
-  if (fn == 2 && fc == 2) return launch_wgrad_x3_t<KX, 2, 2>(a, s);
-  if (fn == 4 && fc == 1) return launch_wgrad_x3_t<KX, 4, 1>(a, s);
-  return launch_wgrad_x3_t<KX, 4, 2>(a, s);
+  if (fn == 1 && fc == 1) return launch_wgrad_x3_t<KX, 1, 1>(a, s, wi);
+  if (fn == 1 && fc == 2) return launch_wgrad_x3_t<KX, 1, 2>(a, s, wi);
+  if (fn == 2 && fc == 1) return launch_wgrad_x3_t<KX, 2, 1>(a, s, wi);
+  if (fn == 2 && fc == 2) return launch_wgrad_x3_t<KX, 2, 2>(a, s, wi);
+  if (fn == 4 && fc == 1) return launch_wgrad_x3_t<KX, 4, 1>(a, s, wi);
+  return launch_wgrad_x3_t<KX, 4, 2>(a, s, wi);
 }
 
 // dst[region at (oz, oy, ox)][cdst + c] += src[..][csrc + c] for c < C (gradient of crop + concat)
@@ -1199,9 +1203,12 @@ __global__ void upsample_bwd_gather_kernel(const float* __restrict__ dout, float
 __global__ void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                             float beta1, float beta2, float eps, float bc1, float bc2_sqrt, float gscale) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
-    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+    // the moments in double, rounded once: in f32 the two terms of m each carry their own roundings, and where the new gradient
+    // opposes the old moment the sum is small beside them, so no f32 form keeps m within a few units of ITS OWN last place
+    // (tests/test_backward_cpu.py); the kernel is bound by its 28 bytes per element, not by these six operations
+    const double gi = (double)g[i] * (double)gscale;
+    const float mi = (float)((double)beta1 * (double)m[i] + (1.0 - (double)beta1) * gi);
+    const float vi = (float)((double)beta2 * (double)v[i] + (1.0 - (double)beta2) * gi * gi);
     m[i] = mi;
     v[i] = vi;
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
@@ -1304,6 +1311,7 @@ struct TrainState {
   float* loss_dev = nullptr;         // [1]
   std::vector<float*> head_out;      // per head: sigmoid outputs [C][D][H][W] of the last forward
   std::vector<float*> head_dp;       // per head: dL/dp
+  std::vector<bsmi_unet_train_step_info> rec;  // what the last pass launched per plan step (bsmi_unet_train_debug_step_info)
   size_t out_vox = 0;
 };
 
@@ -1585,6 +1593,11 @@ int train_refresh_f32_images(bsmi_unet* h, hipStream_t s) {
 
 int train_forward_conv_x3(bsmi_unet* h, const PlanStep& st, hipStream_t s) {
   const TrainFwdX3& fx = *st.tx3;
+  if (h->train && h->train->plan) {  // (a step of the training plan: located by address only after it is known to lie inside it)
+    const std::vector<PlanStep>& steps = h->train->plan->steps;
+    const uintptr_t p0 = (uintptr_t)steps.data(), p1 = (uintptr_t)(steps.data() + steps.size()), ps = (uintptr_t)&st;
+    if (ps >= p0 && ps < p1 && steps.size() == h->train->rec.size()) h->train->rec[(ps - p0) / sizeof(PlanStep)].fwd_split = 1;
+  }
   if (fx.late && h->train && h->train->fwd_packed_pending) {  // the first wide stage after an optimizer step: its image comes from the side stream
     BSMI_HIP(hipStreamWaitEvent(s, h->train->ev_fwd_packed, 0));
     h->train->fwd_packed_pending = false;
@@ -2004,6 +2017,7 @@ int bsmi_unet_train_begin(bsmi_unet* h, const int64_t in_shape[3]) {
 
   // backward data of the conv steps, in plan order; the first CONV step of the plan is the net's first conv
   ts->convs.resize(plan.steps.size());
+  ts->rec.assign(plan.steps.size(), bsmi_unet_train_step_info{});
   bool first_conv = true;
   for (size_t i = 0; i < plan.steps.size(); ++i) {
     const PlanStep& st = plan.steps[i];
@@ -2138,6 +2152,11 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
   const int nheads = (int)h->heads.size();
   const bool det = h->train_det != 0;
   // forward (the inference engine), sigmoid outputs kept for the loss
+  for (size_t i = 0; i < ts->rec.size(); ++i) {
+    ts->rec[i] = bsmi_unet_train_step_info{};
+    ts->rec[i].type = (int32_t)plan.steps[i].type;
+    ts->rec[i].deterministic = det ? 1 : 0;
+  }
   h->train_forward = true;  // CONV steps with a split-bf16 form run it (PlanStep::tx3)
   int rc = bsmi_unet_forward(h, BSMI_PREC_F32, raw_dev, BSMI_RAW_F32, ts->in_shape, ts->head_out.data(), nullptr, stream);
   h->train_forward = false;
@@ -2191,6 +2210,7 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
       case PlanStep::UP: {
         TDesc din = ts->grad_of[st.in.ptr], dout = ts->grad_of[st.out.ptr];
         const size_t total = (size_t)st.out.D * st.out.H * st.out.W * st.out.Cpad;
+        ts->rec[i].up = det ? 2 : 1;
         if (det) {
           const size_t total_in = (size_t)st.in.D * st.in.H * st.in.W * st.in.Cpad;
           hipLaunchKernelGGL(upsample_bwd_gather_kernel, dim3((unsigned)std::min<size_t>((total_in + 255) / 256, 65536)), dim3(256), 0, s,
@@ -2222,6 +2242,10 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
         float* gb = ts->g + param_off(ts, base + ".bias");
         float* gbr = last ? ts->g + param_off(ts, p.prefix + ".residual.0.bias") : nullptr;
         static const bool fuse_colsum = env_on("BSMI_TRAIN_FUSE_COLSUM");
+        bsmi_unet_train_step_info& ri = ts->rec[i];
+        for (int d = 0; d < 3; ++d) ri.border[d] = cb.P[d];
+        ri.has_split = cb.gps ? 1 : 0;
+        ri.bias = (fuse_colsum && !det) ? 1 : 2;
         if (fuse_colsum && !det) {
           // the bias gradient (column sums of g) in the same pass: a grid whose stride is a multiple of the channel groups keeps a
           // thread on its four channels; few workgroups, each ends with one atomic per channel
@@ -2303,6 +2327,7 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
           return grow_buf(sw, &ts->gt_det, &ts->gt_det_bytes, (size_t)det_nz * det_numel * sizeof(float), true);
         };
         // split-bf16 form (wgrad_x3_kernel): pack g once per conv stage, x per launch
+        bsmi_unet_train_wgrad_info* cur_wi = nullptr;  // the record of the launch being issued
         auto wgrad_x3 = [&](const WgradArgs& a) -> int {
           const int gpl = (a.Wo + 7) / 8, nlines = a.Do * a.Ho;
           const int Np = wgrad_pad(a.N, wgrad_tile_n(a.N)), Cp = wgrad_pad(a.C, wgrad_tile_c(a.C)), xvec = a.kx > 1 ? 2 : 1;
@@ -2329,8 +2354,9 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
           k.dwt = det ? (float*)ts->gt_det : a.dwt; k.cin_total = a.cin_total; k.cbase = a.cbase; k.ntap = a.ntap; k.lines_per_block = 0; k.zsplit = 1;
           k.zstride = det ? det_numel : 0;
           if (det) k.zsplit = det_nz;
-          return a.kx == 1 ? launch_wgrad_x3_k<1>(k, sw) : launch_wgrad_x3_k<3>(k, sw);
+          return a.kx == 1 ? launch_wgrad_x3_k<1>(k, sw, cur_wi) : launch_wgrad_x3_k<3>(k, sw, cur_wi);
         };
+        const float* dwm_rec = ts->g + param_off(ts, base + ".weight");
         auto wgrad = [&](const TDesc& x, const int* org, int C, int cbase, float* dw, int ct, const int* kk) {
           WgradArgs a;
           a.g = ginterior; a.gsz = gsz; a.gsy = gsy; a.gsx = gsx;
@@ -2343,6 +2369,11 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
           a.dwt = ts->gt ? ts->gt + (dw - ts->g) : nullptr;
           const int nlines = a.Do * a.Ho;
           const int trows = a.kz * a.ky;
+          cur_wi = ri.n_wgrad < 4 ? &ri.wgrad[ri.n_wgrad++] : nullptr;
+          if (cur_wi) {
+            cur_wi->residual = kk[0] * kk[1] * kk[2] == 1 && dw != dwm_rec ? 1 : 0;
+            cur_wi->n = a.N; cur_wi->c = a.C; cur_wi->cbase = a.cbase;
+          }
           if (a.dwt && (a.kx == 1 || a.kx == 3)) {
             const int rc2 = wgrad_x3(a);
             if (rc2) x3_rc = rc2;
@@ -2356,6 +2387,11 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
           a.lines_per_block = (nlines + zsplit - 1) / zsplit;
           zsplit = (nlines + a.lines_per_block - 1) / a.lines_per_block;
           const dim3 grid(blocks_nc, trows, zsplit);
+          if (cur_wi && a.kx >= 1 && a.kx <= 3) {
+            cur_wi->family = tiled ? BSMI_WGRAD_TILED_F32 : BSMI_WGRAD_WAVE_F32;
+            cur_wi->kx = a.kx; cur_wi->tile_n = tiled ? 128 : 32; cur_wi->tile_c = tiled ? 128 : 64;
+            cur_wi->ranges = zsplit; cur_wi->lines_per_range = a.lines_per_block;
+          }
           if (tiled) {
             switch (a.kx) {
               case 1: hipLaunchKernelGGL(wgrad_tiled_kernel<1>, grid, dim3(256), 0, sw, a); break;
@@ -2411,6 +2447,14 @@ int bsmi_unet_train_forward_backward(bsmi_unet* h, const float* raw_dev, const f
         if (cb.need_dgrad) {
           rc = launch_conv_igemm(cb.dgrad, cb.dx3 ? BSMI_PREC_BF16X3 : BSMI_PREC_F32, cb.dtile, s, h->sk_ws, h->sk_grid);
           if (rc) return rc;
+          ri.dgrad = cb.dx3 ? 2 : 1;
+          ri.dgrad_raw = cb.dgrad.raw ? 1 : 0;
+          ri.dgrad_converted = cb.dsplit ? 1 : 0;
+          ri.dgrad_bn = tile_bn(cb.dtile);
+          ri.dgrad_ksteps = cb.dgrad.nsteps;
+          ri.dgrad_split_k = conv_igemm_split_k(cb.dgrad, cb.dx3 ? BSMI_PREC_BF16X3 : BSMI_PREC_F32, cb.dtile, h->sk_grid > 0 ? h->sk_grid : 0) ? 1 : 0;
+          ri.dgrad_scatter = cb.scatter ? 1 : 0;
+          ri.dgrad_residual = (ci == 0 && n > 1) ? 1 : 0;
           if (cb.dsplit) {
             const size_t g8 = (size_t)cb.dcat.D * cb.dcat.H * cb.dcat.W * cb.dcat.Cpad / 8;
             hipLaunchKernelGGL(split_to_f32_kernel, dim3((unsigned)std::min<size_t>((g8 + 255) / 256, 16384)), dim3(256), 0, s,
@@ -2536,6 +2580,133 @@ int bsmi_unet_train_adam_step(bsmi_unet* h, float lr, float beta1, float beta2, 
                        (long long)param_off(ts, pre + ".conv_pass.0.bias"), (long long)param_off(ts, pre + ".residual.0.bias"), hd.cout, hd.cin, hd.hw, hd.hb);
   }
   BSMI_HIP(hipGetLastError());
+  return BSMI_OK;
+}
+
+int bsmi_unet_train_debug_step_info(bsmi_unet* h, int step, bsmi_unet_train_step_info* info) {
+  if (!h || !h->train || !info) BSMI_FAIL(BSMI_ERR_STATE, "bsmi_unet_train_begin has not been called / null argument");
+  if (step < 0 || step >= (int)h->train->rec.size()) BSMI_FAIL(BSMI_ERR_INVALID, "step %d out of range (%zu steps)", step, h->train->rec.size());
+  *info = h->train->rec[step];
+  return BSMI_OK;
+}
+
+int bsmi_unet_train_debug_tensor(bsmi_unet* h, int step, int what, int64_t shape_out[4], float* host_out, uint64_t capacity) {
+  if (!h || !h->train || !shape_out) BSMI_FAIL(BSMI_ERR_STATE, "bsmi_unet_train_begin has not been called / null argument");
+  TrainState* ts = h->train;
+  Plan& plan = *ts->plan;
+  if (step < 0 || step >= (int)plan.steps.size()) BSMI_FAIL(BSMI_ERR_INVALID, "step %d out of range (%zu steps)", step, plan.steps.size());
+  const PlanStep& st = plan.steps[step];
+  const ConvBwd* cb = st.type == PlanStep::CONV ? &ts->convs[step] : nullptr;
+  BSMI_HIP(hipSetDevice(h->device));
+  auto fetch = [&](const void* ptr, size_t floats, std::vector<float>& raw) -> int {
+    raw.resize(floats);
+    BSMI_HIP(hipDeviceSynchronize());  // every stream of the device, the weight gradients' own included
+    BSMI_HIP(hipMemcpy(raw.data(), ptr, floats * sizeof(float), hipMemcpyDeviceToHost));
+    return BSMI_OK;
+  };
+  auto find_grad = [&](const TDesc& act, TDesc* out) {
+    auto it = ts->grad_of.find(act.ptr);
+    if (it == ts->grad_of.end()) return false;
+    *out = it->second;
+    return true;
+  };
+  int rc;
+  std::vector<float> raw;
+  if (what == BSMI_TRAIN_DBG_HEAD_DP) {
+    if (st.type != PlanStep::HEAD) BSMI_FAIL(BSMI_ERR_STATE, "step %d is no head", step);
+    const int co = h->heads[st.head].cout;
+    shape_out[0] = st.in.D; shape_out[1] = st.in.H; shape_out[2] = st.in.W; shape_out[3] = co;
+    if (!host_out) return BSMI_OK;
+    if (capacity < ts->out_vox * co) BSMI_FAIL(BSMI_ERR_INVALID, "buffer of %llu floats too small", (unsigned long long)capacity);
+    if ((rc = fetch(ts->head_dp[st.head], ts->out_vox * co, raw))) return rc;
+    for (size_t v = 0; v < ts->out_vox; ++v)
+      for (int c = 0; c < co; ++c) host_out[v * co + c] = raw[(size_t)c * ts->out_vox + v];
+    return BSMI_OK;
+  }
+  if (what == BSMI_TRAIN_DBG_PAD_COUNT) {
+    if (!cb || !cb->st) BSMI_FAIL(BSMI_ERR_STATE, "step %d is no conv step", step);
+    shape_out[0] = shape_out[1] = shape_out[2] = 1; shape_out[3] = 4;
+    if (!host_out) return BSMI_OK;
+    if (capacity < 4) BSMI_FAIL(BSMI_ERR_INVALID, "buffer of %llu floats too small", (unsigned long long)capacity);
+    auto pad_channels = [&](const TDesc& t, const std::vector<float>& a) {
+      size_t cnt = 0;
+      const size_t nv = (size_t)t.D * t.H * t.W;
+      for (size_t v = 0; v < nv; ++v)
+        for (int c = t.C; c < t.Cpad; ++c) cnt += a[v * t.Cpad + c] != 0.f;
+      return cnt;
+    };
+    const TDesc& g = cb->gp;
+    if ((rc = fetch(g.ptr, (size_t)g.D * g.H * g.W * g.Cpad, raw))) return rc;
+    host_out[0] = (float)pad_channels(g, raw);
+    size_t border = 0;
+    for (int z = 0; z < g.D; ++z)
+      for (int y = 0; y < g.H; ++y)
+        for (int x = 0; x < g.W; ++x) {
+          const bool inside = z >= cb->P[0] && z < g.D - cb->P[0] && y >= cb->P[1] && y < g.H - cb->P[1] && x >= cb->P[2] && x < g.W - cb->P[2];
+          if (inside) continue;
+          const float* r = raw.data() + (((size_t)z * g.H + y) * g.W + x) * g.Cpad;
+          for (int c = 0; c < g.Cpad; ++c) border += r[c] != 0.f;
+        }
+    host_out[1] = (float)border;
+    TDesc gy;
+    host_out[2] = 0.f;
+    if (find_grad(st.out, &gy)) {
+      if ((rc = fetch(gy.ptr, (size_t)gy.D * gy.H * gy.W * gy.Cpad, raw))) return rc;
+      host_out[2] = (float)pad_channels(gy, raw);
+    }
+    host_out[3] = 0.f;
+    if (cb->dcat.ptr) {
+      if ((rc = fetch(cb->dcat.ptr, (size_t)cb->dcat.D * cb->dcat.H * cb->dcat.W * cb->dcat.Cpad, raw))) return rc;
+      host_out[3] = (float)pad_channels(cb->dcat, raw);
+    }
+    return BSMI_OK;
+  }
+  TDesc t;
+  bool split = false;
+  switch (what) {
+    case BSMI_TRAIN_DBG_DOUT:
+      if (st.type == PlanStep::HEAD || !find_grad(st.out, &t)) BSMI_FAIL(BSMI_ERR_STATE, "step %d has no output gradient tensor", step);
+      break;
+    case BSMI_TRAIN_DBG_GMASK:
+      if (!cb || !cb->st) BSMI_FAIL(BSMI_ERR_STATE, "step %d is no conv step", step);
+      t = cb->gp;
+      break;
+    case BSMI_TRAIN_DBG_GSPLIT: case BSMI_TRAIN_DBG_GSPLIT_HI: case BSMI_TRAIN_DBG_GSPLIT_LO:
+      if (!cb || !cb->st || !cb->gps) BSMI_FAIL(BSMI_ERR_STATE, "step %d has no split copy of its masked gradient", step);
+      t = cb->gp;
+      t.ptr = cb->gps;
+      split = true;
+      break;
+    case BSMI_TRAIN_DBG_DCAT:
+      if (!cb || !cb->st || !cb->scatter || !cb->dcat.ptr) BSMI_FAIL(BSMI_ERR_STATE, "step %d has no concat-input gradient", step);
+      t = cb->dcat;
+      break;
+    default: BSMI_FAIL(BSMI_ERR_INVALID, "unknown tensor %d", what);
+  }
+  shape_out[0] = t.D; shape_out[1] = t.H; shape_out[2] = t.W; shape_out[3] = t.C;
+  if (!host_out) return BSMI_OK;
+  const size_t nvox = (size_t)t.D * t.H * t.W;
+  if (capacity < nvox * t.C) BSMI_FAIL(BSMI_ERR_INVALID, "buffer of %llu floats too small", (unsigned long long)capacity);
+  if ((rc = fetch(t.ptr, nvox * t.Cpad, raw))) return rc;  // (the split layout keeps 4 bytes per channel)
+  const uint16_t* r16 = (const uint16_t*)raw.data();
+  auto bf16_value = [](uint16_t b) {
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    memcpy(&f, &u, sizeof f);
+    return f;
+  };
+  for (size_t v = 0; v < nvox; ++v)
+    for (int c = 0; c < t.C; ++c) {
+      float x;
+      if (!split) {
+        x = raw[v * t.Cpad + c];
+      } else {  // (hi, lo) vectors of 8 interleaved (conv_dev.h act_index)
+        const size_t i = 2 * v * t.Cpad + (size_t)((c >> 3) << 4) + (c & 7);
+        const float hi = bf16_value(r16[i]), lo = bf16_value(r16[i + 8]);
+        x = what == BSMI_TRAIN_DBG_GSPLIT_HI ? hi : (what == BSMI_TRAIN_DBG_GSPLIT_LO ? lo : hi + lo);
+      }
+      host_out[v * t.C + c] = x;
+    }
   return BSMI_OK;
 }
 

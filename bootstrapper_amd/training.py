@@ -319,6 +319,42 @@ class Trainer:
         check(lib.bsmi_unet_train_read_param(self.model._h, key.encode(), idx, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def debug_tensor(self, step, what="dout"):
+        """Development aid: a gradient tensor of plan step `step` (numbering of Model.plan_steps) as the last forward_backward
+        left it, float32 (D, H, W, C): "dout" dL/d(output), "gmask" the padded masked gradient of a conv step with its border,
+        "gsplit" / "gsplit_hi" / "gsplit_lo" its split-bf16 copy, "dcat" the concat-input gradient of a pass's first stage,
+        "head_dp" dL/dp of a head, "pad_count" the non-zero values among those the kernels read as zeros (padding channels of
+        the masked gradient, its border, padding channels of dout and of dcat).  Synchronises the device."""
+        w = _lib.TRAIN_TENSORS[what]
+        shape = (C.c_int64 * 4)()
+        check(lib.bsmi_unet_train_debug_tensor(self.model._h, int(step), w, shape, None, 0))
+        out = np.empty(tuple(shape), dtype=np.float32)
+        check(lib.bsmi_unet_train_debug_tensor(self.model._h, int(step), w, shape, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def backward_steps(self):
+        """What the last backward pass launched, per plan step, as dicts (bsmi_unet_train_debug_step_info): conv steps carry
+        `wgrad` (one dict per weight-gradient launch: family, residual, n, c, cbase, kx, tile, ranges, lines_per_range,
+        det_workspace), `dgrad` (None or a dict: arithmetic, raw, converted, bn, ksteps, split_k, scatter, residual), `border`,
+        `has_split`, `bias` ("fused" / "colsum"), `fwd_split`; up steps `up` ("scatter" / "gather")."""
+        out = []
+        for i in range(len(self.model.plan_steps())):
+            si = _lib.TrainStepInfo()
+            check(lib.bsmi_unet_train_debug_step_info(self.model._h, i, C.byref(si)))
+            d = {"step": i, "type": _lib.STEP_TYPES[si.type], "deterministic": bool(si.deterministic)}
+            if d["type"] == "conv":
+                d["wgrad"] = [dict(family=_lib.WGRAD_FAMILIES[w.family], residual=bool(w.residual), n=w.n, c=w.c, cbase=w.cbase, kx=w.kx,
+                                   tile=(w.tile_n, w.tile_c), ranges=w.ranges, lines_per_range=w.lines_per_range,
+                                   det_workspace=bool(w.det_workspace)) for w in list(si.wgrad)[:si.n_wgrad]]
+                d["dgrad"] = None if not si.dgrad else dict(
+                    arithmetic=("f32", "split-bf16")[si.dgrad - 1], raw=bool(si.dgrad_raw), converted=bool(si.dgrad_converted), bn=si.dgrad_bn,
+                    ksteps=si.dgrad_ksteps, split_k=bool(si.dgrad_split_k), scatter=bool(si.dgrad_scatter), residual=bool(si.dgrad_residual))
+                d.update(border=tuple(si.border), has_split=bool(si.has_split), bias=(None, "fused", "colsum")[si.bias], fwd_split=bool(si.fwd_split))
+            elif d["type"] == "up":
+                d["up"] = (None, "scatter", "gather")[si.up]
+            out.append(d)
+        return out
+
     def write(self, key, what, values):
         """restore an Adam moment ("exp_avg" / "exp_avg_sq") of one parameter"""
         idx = {"exp_avg": 2, "exp_avg_sq": 3}[what]

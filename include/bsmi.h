@@ -156,6 +156,54 @@ int bsmi_unet_train_write_param(bsmi_unet *h, const char *key, int what, const f
 int bsmi_unet_train_step_count(bsmi_unet *h, int set_to, int *value);
 int bsmi_unet_train_end(bsmi_unet *h);
 
+/* Development aid (read-only): a gradient tensor of plan step `step` (numbering of bsmi_unet_debug_step_info) as the last
+ * bsmi_unet_train_forward_backward left it, float32 channels-last [D][H][W][C] on the host, real channels only.  Every such
+ * tensor is allocated once in bsmi_unet_train_begin and stays resident, so this only copies; it synchronises the device
+ * (the weight gradients' side stream included).  shape_out = {D, H, W, C}; host_out may be NULL to query the shape.
+ * A step that has no such tensor fails with BSMI_ERR_STATE. */
+enum {
+  BSMI_TRAIN_DBG_DOUT = 0,      /* dL/d(output of the step); conv, pool and up steps, and the net's input where it has one */
+  BSMI_TRAIN_DBG_GMASK = 1,     /* conv: the padded masked gradient dY [Y > 0], whole, zero border included */
+  BSMI_TRAIN_DBG_GSPLIT = 2,    /* conv: its split-bf16 copy as hi + lo (where the input gradient is a split launch) */
+  BSMI_TRAIN_DBG_GSPLIT_HI = 3, /* ... the hi plane */
+  BSMI_TRAIN_DBG_GSPLIT_LO = 4, /* ... the lo plane */
+  BSMI_TRAIN_DBG_DCAT = 5,      /* conv 0 of a ConvPass: the gradient of its (cropped, concatenated) input before the scatter */
+  BSMI_TRAIN_DBG_HEAD_DP = 6,   /* head: dL/dp */
+  BSMI_TRAIN_DBG_PAD_COUNT = 7  /* conv: shape {1, 1, 1, 4}: the number of non-zero values the kernels read as zeros -- in the
+                                 * padding channels (C .. Cpad) of the masked gradient, in its border (all channels), in the
+                                 * padding channels of the output gradient, and of the concat-input gradient (0 without one) */
+};
+int bsmi_unet_train_debug_tensor(bsmi_unet *h, int step, int what, int64_t shape_out[4], float *host_out,
+                                 uint64_t capacity);
+
+/* What the last backward pass ran for plan step `step`, recorded where each launch was issued. */
+enum { BSMI_WGRAD_NONE = 0, BSMI_WGRAD_WAVE_F32 = 1, BSMI_WGRAD_TILED_F32 = 2, BSMI_WGRAD_SPLIT = 3 };
+typedef struct {
+  int32_t family;          /* BSMI_WGRAD_* */
+  int32_t residual;        /* 1: a slot of the cropped 1x1x1 residual branch */
+  int32_t n, c, cbase;     /* real output / input channels of the slot, its first column in the weight */
+  int32_t kx;              /* x taps one workgroup accumulates */
+  int32_t tile_n, tile_c;  /* (n, c) block of one workgroup */
+  int32_t ranges, lines_per_range;  /* line ranges the launch was cut into, output lines (z, y) in each */
+  int32_t det_workspace;   /* 1: every range added into its own copy of the workspace (deterministic mode) */
+} bsmi_unet_train_wgrad_info;
+typedef struct {
+  int32_t type;            /* BSMI_STEP_* */
+  int32_t n_wgrad;         /* conv: weight-gradient launches, main slots first, then the residual's */
+  bsmi_unet_train_wgrad_info wgrad[4];
+  int32_t dgrad;           /* conv: input gradient 0 none, 1 exact f32, 2 split-bf16 */
+  int32_t dgrad_raw;       /* split: the launch stored raw f32 sums */
+  int32_t dgrad_converted; /* split: (hi, lo) pairs, then split_to_f32_kernel */
+  int32_t dgrad_bn, dgrad_ksteps, dgrad_split_k, dgrad_scatter, dgrad_residual;
+  int32_t border[3];       /* conv: border of the padded masked gradient */
+  int32_t has_split;       /* conv: a split copy of the masked gradient exists */
+  int32_t bias;            /* conv: bias sums 0 none, 1 fused into the masking pass, 2 colsum_kernel */
+  int32_t up;              /* up: 0 none, 1 scatter (float atomics), 2 gather */
+  int32_t fwd_split;       /* conv: the training forward ran this step as a fused split-bf16 launch */
+  int32_t deterministic;
+} bsmi_unet_train_step_info;
+int bsmi_unet_train_debug_step_info(bsmi_unet *h, int step, bsmi_unet_train_step_info *info);
+
 /* Affinity training targets of one sample, on the device (reference models/3d_affs/train.py:127-139:
  * gp.GrowBoundary(labels, mask=unlabelled, steps, only_xy) -> gp.AddAffinities(neighborhood) ->
  * gp.BalanceLabels; the erosion as in gp/custom_grow_boundary.py:71-110 with a fixed step count).

@@ -220,6 +220,11 @@ def _load():
         "bsmi_synth_stamp_i64": (i32, [i32, vp, i64p, i32, i32, i32, vp, i32, i32, C.c_int64, vp]),
         "bsmi_synth_present_i64": (i32, [p, vp, C.c_uint64, vp, C.c_uint32, C.POINTER(C.c_uint32), vp]),
         "bsmi_synth_split_i64": (i32, [p, vp, i64p, C.c_int64, i32, C.POINTER(C.c_int32), i32, C.c_int64, C.POINTER(C.c_uint64), vp]),
+        "bsmi_aug_coords": (i32, [i32, i64p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), i32, i32, vp, vp,
+                                  C.POINTER(C.c_int32), C.POINTER(C.c_float), vp, vp]),
+        "bsmi_aug_sample_f32_u8": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
+        "bsmi_aug_sample_nearest_i64": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
+        "bsmi_aug_sample_nearest_u8": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

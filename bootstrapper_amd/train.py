@@ -5,11 +5,14 @@ Reference being mirrored (paths relative to /root/reference/bootstrapper):
   models/3d_affs/train.py:160-199 train(setup_dir, voxel_size, max_iterations, samples, save_checkpoints_every, ...)
   training.py:96-137              fit(): seed 42, checkpoints `model_checkpoint_<step>`, resume from the latest one
 
-What is NOT restated: the gunpowder augmentation chain of models/3d_affs/train.py:88-117 (SimpleAugment,
-DeformAugment, ShiftAugment, noise / intensity / gamma / impulse / smooth / defect augmentations) and the snapshot
-callback -- third-party pipeline code outside the hot path.  `SampleSource` does the deterministic part only: random
-location with the >= 5 % labelled-voxel rejection, Normalize + IntensityScaleShift(2, -1), then GrowBoundary,
-AddAffinities on the configured neighbourhood and BalanceLabels in one device call (`affinity_targets`).  `SectionSource`
+What is NOT restated: the intensity nodes of the gunpowder chain of models/3d_affs/train.py:105-120 (noise / intensity /
+gamma / impulse / smooth / defect augmentations) and the snapshot callback -- third-party pipeline code outside the hot
+path.  `SampleSource` does the deterministic part: random location with the >= 5 % labelled-voxel rejection, Normalize +
+IntensityScaleShift(2, -1), then GrowBoundary, AddAffinities on the configured neighbourhood and BalanceLabels in one
+device call (`affinity_targets`).  With the train config key `augment` it also applies the geometric chain of
+models/3d_affs/train.py:95-104 (SimpleAugment -> DeformAugment -> ShiftAugment) on the device, as one coordinate map
+(augment.py, csrc/augment.hip; specified rules); without the key the batches are un-augmented
+crops, as before.  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
 of each section in one launch each (csrc/train2d.hip).  `SyntheticSource` feeds the second-stage setups
 (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
@@ -312,7 +315,9 @@ class SampleSource:
     """Infinite iterator of reference-style batches from (raw, labels[, mask]) Zarr volumes."""
 
     def __init__(self, samples, input_shape, output_shape, neighborhood, device=0, seed=42, head="affs", grow_boundary=0,
-                 lsd_sigma=None, lsd_downsample=1, voxel_size=(1, 1, 1)):
+                 lsd_sigma=None, lsd_downsample=1, voxel_size=(1, 1, 1), augment=None):
+        """augment: an augment.AugParams (or True for the reference's arguments) turns on the geometric chain SimpleAugment ->
+        DeformAugment -> ShiftAugment (augment.py); None: un-augmented crops, the same batches as without the argument."""
         self.samples = [(open_ds(s["raw"]), open_ds(s["labels"]), open_ds(s["mask"]) if s.get("mask") else None) for s in samples]
         self.inp, self.out = tuple(input_shape), tuple(output_shape)
         self.nhood = [list(map(int, o)) for o in neighborhood]
@@ -327,11 +332,97 @@ class SampleSource:
         self.voxel_size = tuple(float(v) for v in voxel_size)
         if head != "affs" and lsd_sigma is None:
             raise ValueError("the LSD head needs net_config outputs.3d_lsds.sigma")
+        self.augment = None
+        if augment is not None and augment is not False:
+            from . import augment as aug
+            self.augment = aug.AugParams() if augment is True else augment
+            # refusals before any read: a swap of non-square blocks, a rotation on an anisotropic section grid, an LSD
+            # context that the coordinate volume (the input block) does not cover
+            if self.augment.simple:
+                aug.check_square(self.inp, self.out)
+            if self.augment.deform_p > 0 and self.augment.rotate and self.voxel_size[1] != self.voxel_size[2]:
+                raise NotImplementedError(f"rotation about z needs voxel_size[1] == voxel_size[2], not {list(self.voxel_size)}; set "
+                                          "augment.rotate = false (full 3-D rotations are not built)")
+            ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
+            if any((i - o) % 2 for i, o in zip(self.inp, self.out)):
+                raise ValueError(f"augment: input_shape {list(self.inp)} - output_shape {list(self.out)} must be even on every axis")
+            if any(c > x for c, x in zip(self._lsd_context(), ctx)):
+                raise ValueError(f"augment: the LSD context {self._lsd_context()} exceeds the network's context {ctx}; the labels are "
+                                 "resampled through the coordinates of the input block")
+
+    def _lsd_context(self):
+        """voxels of labels the descriptors need beyond the output block: 3 sigma, snapped to the sub-sampling grid; 0 without an LSD head"""
+        if self.head == "affs":
+            return [0, 0, 0]
+        sig = [float(self.lsd_sigma)] * 3 if isinstance(self.lsd_sigma, (int, float)) else list(self.lsd_sigma)
+        return [-(-int(-(-3.0 * s // v)) // self.lsd_df) * self.lsd_df for s, v in zip(sig, self.voxel_size)]
 
     def __iter__(self):
         return self
 
+    @staticmethod
+    def _read_padded(ds, lo, shape, dtype):
+        """ds[lo : lo + shape] in voxels of its last three axes, zeros beyond the volume (gp.Pad(x, None))"""
+        out = np.zeros(shape, dtype=dtype)
+        src, dst = [], []
+        for a, n, m in zip(lo, shape, ds.shape[-3:]):
+            b0, b1 = max(a, 0), min(a + n, m)
+            if b1 <= b0:
+                return out
+            src.append(slice(b0, b1))
+            dst.append(slice(b0 - a, b1 - a))
+        out[tuple(dst)] = ds[tuple(src)]
+        return out
+
+    def _next_augmented(self):
+        """One batch through the geometric chain: location and plan drawn from self.rng (location first, then
+        augment.draw_plan's order), one crop of raw, labels and mask -- augment.source_box of the plan, zeros beyond the
+        volume -- uploaded, one coordinate launch, one resampling launch per array, the usual targets on the augmented
+        labels and mask.  The 5 % test sees the augmented output block; a failing draw is redrawn, location and plan."""
+        from . import augment as aug
+        ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
+        cv = self._lsd_context()
+        for _ in range(1000):
+            raw_ds, lab_ds, mask_ds = self.samples[self.rng.integers(len(self.samples))]
+            shape = lab_ds.shape[-3:]
+            if any(s < o for s, o in zip(shape, self.out)):
+                raise ValueError("labels volume smaller than the network's output block")
+            off = [int(self.rng.integers(0, s - o + 1)) for s, o in zip(shape, self.out)]
+            plan = aug.draw_plan(self.rng, self.augment, self.inp, self.voxel_size)
+            lo, hi = aug.source_box(plan)
+            start = [a - c + l for a, c, l in zip(off, ctx, lo)]      # the crop's origin in voxels of the volume
+            size = tuple(h - l for l, h in zip(lo, hi))
+            coords = aug.coords(plan, lo, self.dev)
+            # labels and mask over the output block grown by the LSD context, all from the one coordinate volume
+            region = ([c - v for c, v in zip(ctx, cv)], [o + 2 * v for o, v in zip(self.out, cv)])
+            lab_np = self._read_padded(lab_ds, start, size, lab_ds.dtype)
+            # uint64 ids reinterpreted, not converted: the same bits as astype(int64) without a second copy of the crop
+            lab_crop = torch.from_numpy(lab_np.view(np.int64) if lab_np.dtype == np.uint64 else lab_np.astype(np.int64, copy=False)).to(self.dev)
+            big = aug.sample_labels(coords, lab_crop, region)
+            if mask_ds is not None:
+                mask_crop = torch.from_numpy((self._read_padded(mask_ds, start, size, mask_ds.dtype) > 0).astype(np.uint8)).to(self.dev)
+                bun = aug.sample_mask(coords, mask_crop, region)
+            else:
+                bun = (big > 0).to(torch.uint8)
+            inner = tuple(slice(v, v + o) for v, o in zip(cv, self.out))
+            unl_dev = bun[inner].contiguous()
+            if float(unl_dev.float().mean()) < 0.05:   # gp.Reject(mask=unlabelled, min_masked=0.05), on the augmented block
+                continue
+            raw_crop = torch.from_numpy(self._read_padded(raw_ds, start, size, np.uint8)).to(self.dev)
+            batch = {"raw": aug.sample_raw(coords, raw_crop)}
+            if self.head != "affs":
+                sig = [float(self.lsd_sigma)] * 3 if isinstance(self.lsd_sigma, (int, float)) else list(self.lsd_sigma)
+                lsds, lw = lsd_targets(big, cv, self.out, sig, self.voxel_size, self.lsd_df, bun)
+                batch.update(gt_lsds=lsds, lsds_weights=lw)
+            if self.head != "lsds":
+                affs, weights = affinity_targets(big[inner].contiguous(), unl_dev, self.nhood, self.grow, only_xy=True)
+                batch.update(gt_affs=affs, affs_weights=weights)
+            return batch
+        raise RuntimeError("no training location with at least 5 % labelled voxels found")
+
     def __next__(self):
+        if self.augment is not None:
+            return self._next_augmented()
         ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
         for _ in range(1000):
             raw_ds, lab_ds, mask_ds = self.samples[self.rng.integers(len(self.samples))]
@@ -558,6 +649,15 @@ def make_sample_source(config, net_config, device=0, rank=0):
     """The built-in sample stream of `bs train` for this rank: seed 42 + rank, so that data-parallel ranks see different
     samples (with one seed for all, the averaged gradient would be the single-rank gradient computed N times)."""
     outs = net_config["outputs"]
+    from .augment import AugParams
+    augment = AugParams.from_config(config.get("augment"))
+    if augment is not None:
+        if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
+            raise NotImplementedError(f"augment: not built for synthetic labels (SyntheticSource, the {setup_name(net_config)} setup); "
+                                      "it covers 3d_affs, 3d_lsd and 3d_mtlsd")
+        if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
+            raise NotImplementedError(f"augment: not built for the 2-D setups (SectionSource, {setup_name(net_config)}); "
+                                      "it covers 3d_affs, 3d_lsd and 3d_mtlsd")
     if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
         if not config.get("synthetic_labels", False):
             raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
@@ -576,7 +676,7 @@ def make_sample_source(config, net_config, device=0, rank=0):
     return SampleSource(config["samples"], net_config["input_shape"], net_config["output_shape"], nhood, device=device,
                         seed=42 + int(rank), head=head, grow_boundary=int(out3d.get("grow_boundary", 0)) if out3d else 0,
                         lsd_sigma=lsd3d.get("sigma") if lsd3d else None, lsd_downsample=int(lsd3d.get("downsample", 1)) if lsd3d else 1,
-                        voxel_size=config.get("voxel_size", (1, 1, 1)))
+                        voxel_size=config.get("voxel_size", (1, 1, 1)), augment=augment)
 
 
 def default_init(net_config, seed=42):
@@ -653,7 +753,12 @@ def run_training(config_file, device=0, batches=None, log=print):
     if ckpt and load_optimizer_state(trainer, ckpt):
         log(f"optimizer state restored (step {trainer.step_count()})")
     if batches is None:
-        log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops")
+        if config.get("augment"):
+            from .augment import NOT_BUILT
+            log(f"note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`); not built: {NOT_BUILT}")
+        else:
+            log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
+                "(`augment = true` turns on the geometric chain of the 3-D setups)")
         batches = make_sample_source(config, net_config, device, rank)
         if isinstance(batches, SyntheticSource):
             log(f"note: synthetic labels (synthetic_labels = true); not built: {SyntheticSource.NOT_BUILT}")

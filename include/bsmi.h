@@ -812,6 +812,46 @@ int bsmi_synth_present_i64(bsmi_synth *h, const int64_t *labels_dev, uint64_t n_
 int bsmi_synth_split_i64(bsmi_synth *h, int64_t *labels_dev, const int64_t shape[3], int64_t id, int window, const int32_t *sections,
                          int n_sections, int64_t scale, uint64_t *num_host, void *stream);
 
+/* ---- training augmentation: the geometric chain of the first-stage 3-D setups (csrc/augment.hip; reference
+ * models/3d_affs/train.py:95-104: SimpleAugment -> DeformAugment -> ShiftAugment; the rules in full: DESIGN.md section
+ * 7j, tests/aug_ref.py) ----
+ * The three nodes compose into one coordinate map, so a sample costs one coordinate launch and one resampling launch per
+ * array.  These are specified rules: parity with gunpowder is in distribution, not draw by draw.  Every random scalar
+ * is drawn by the caller.  Stateless, asynchronous on `stream`; volumes are [D][H][W].
+ *
+ * aug_coords writes s(p), the source coordinate in voxels of the crop, for every voxel p = (z, y, x) of a block of
+ * `shape`, as three float32 planes coords_dev [3][D][H][W] (z, y, x), all arithmetic in float32:
+ *   r = p + (0, shifts[0][p_z], shifts[1][p_z])            shifts_dev: int32 [2][D] (y, x per section) or NULL (none)
+ *   d = r - centre                                         centre = (shape - 1) / 2
+ *   t = (l0 * d_z, l1 * d_y + l2 * d_x, l3 * d_y + l4 * d_x) + E(r)
+ *                                                          linear = (l0 .. l4) = u * (1, cos, -sin, sin, cos) of a
+ *                                                          scaling by u and a rotation about z
+ *   E(r): trilinear interpolation of lattice_dev, float32 [3][nz][ny][nx] (component z, y, x in voxels), or 0 when
+ *         lattice_dev is NULL.  Per axis g = r * inv_spacing + org, clamped to [0, n - 1]; org = 1 (node 0 lies one spacing
+ *         before the block) or 0 on an axis of one node; cell = min(floor(g), max(n - 2, 0)), weight g - cell,
+ *         a + w * (b - a) along x, then y, then z.  nz * ny * nx <= 4096 (48 KiB of LDS), else BSMI_ERR_INVALID.
+ *   if swap_yx: t_y <-> t_x (needs shape[1] == shape[2], else BSMI_ERR_INVALID)
+ *   s = src_centre + (mirror bit a set ? -t_a : t_a)        mirror: bit 0 / 1 / 2 = z / y / x; src_centre: the block's
+ *                                                          centre in voxels of the crop
+ * aug_sample_* read coords_dev (of coords_shape) at the voxels [region_offset, region_offset + region_shape) -- so one
+ * coordinate volume serves the input block, the output block and the LSD region -- and a crop of crop_shape; out_dev has
+ * region_shape.  Every index is clamped to the crop: a wrong coordinate can give a wrong sample, never a read outside.
+ *   f32_u8:      trilinear, cell floor(s), both corners clamped, a + w * (b - a) along x, y, z; out = (v * 2 - 255) / 255
+ *                (v * 2 / 255 - 1 in one rounded division: within half an ulp where s is a voxel centre).
+ *   nearest_i64, nearest_u8: crop[clamp(floor(s + 0.5))] per axis, the sum and the floor in float32.
+ * A block, a crop or a region holds fewer than 2^31 voxels. */
+int bsmi_aug_coords(int device, const int64_t shape[3], const float linear[5], const float centre[3], const float src_centre[3], int mirror,
+                    int swap_yx, const int32_t *shifts_dev, const float *lattice_dev, const int32_t lattice_shape[3], const float inv_spacing[3],
+                    float *coords_dev, void *stream);
+int bsmi_aug_sample_f32_u8(int device, const float *coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
+                           const int64_t region_shape[3], const uint8_t *crop_dev, const int64_t crop_shape[3], float *out_dev, void *stream);
+int bsmi_aug_sample_nearest_i64(int device, const float *coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
+                                const int64_t region_shape[3], const int64_t *crop_dev, const int64_t crop_shape[3], int64_t *out_dev,
+                                void *stream);
+int bsmi_aug_sample_nearest_u8(int device, const float *coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
+                               const int64_t region_shape[3], const uint8_t *crop_dev, const int64_t crop_shape[3], uint8_t *out_dev,
+                               void *stream);
+
 #ifdef __cplusplus
 }
 #endif

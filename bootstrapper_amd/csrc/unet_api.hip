@@ -255,6 +255,12 @@ static int wino_mode() {
   static const int m = [] { const char* e = getenv("BSMI_WINO"); return e ? atoi(e) : 1; }();
   return m;
 }
+// The last stage of a decoder ConvPass is a special case (wino_narrow_last below): behind a (1,2,2) upsampling it runs in
+// Winograd form whenever the pass's first stage does, whatever its own cin * cout, because only then can Planner::rec fuse the
+// upsampling into the pass -- and the upsampled map, its launch and three quarters of the first stage's source reads, is what
+// the pass spends most on (360 -> 60, 60 -> 60 of the 128^3 block: DESIGN.md section 6).  Such a stage takes the form ONLY
+// behind a fused upsampling (PackedWino::fused_only); every other site keeps the thresholds below, the encoder's 60 -> 60
+// stage among them.
 static int wino4_mode();
 static bool wino_eligible(const PassSite& p, int ci) {
   if (wino_mode() == 0 || p.k[ci][0] != 3 || p.k[ci][1] != 3 || p.k[ci][2] != 3) return false;
@@ -288,6 +294,22 @@ static int wino_tile_edge(const PassSite& p, int ci) {
   return wino4_mode() == 0 ? 2 : 4;
 }
 
+// BSMI_FUSE_UP_NARROW=0: a decoder pass fuses its upsampling only when its last stage is a Winograd stage by wino_eligible's own
+// thresholds (the rule before this one; kept for A/B runs and as the cross-check).
+static bool fuse_up_narrow() {
+  static const bool on = [] { const char* e = getenv("BSMI_FUSE_UP_NARROW"); return !(e && e[0] == '0'); }();
+  return on;
+}
+// The narrow last stage of decoder pass `p` that takes the Winograd form for the sake of the fused upsampling.
+static bool wino_narrow_last(const bsmi_unet* h, const PassSite& p, int ci) {
+  if (!fuse_up_narrow() || wino_mode() == 0 || p.nslots != 2 || p.nconv < 2 || ci != p.nconv - 1) return false;
+  if (&p < h->r_conv.data() || &p >= h->r_conv.data() + h->r_conv.size()) return false;
+  const int* f = h->cfg.downsample_factors[&p - h->r_conv.data()];
+  if (f[0] != 1 || f[1] != 2 || f[2] != 2) return false;   // what Planner::rec can fuse
+  if (p.k[ci][0] != 3 || p.k[ci][1] != 3 || p.k[ci][2] != 3 || p.cout < 32 || !x3_fused_for(choose_tile(p.cout))) return false;
+  return wino_eligible(p, 0) && !wino_eligible(p, ci);
+}
+
 static int pack_wino(bsmi_unet* h, PassSite& p, int ci) {
   PackedWino& pw = p.wino[ci];
   if (pw.w) { (void)hipFree(pw.w); pw.w = nullptr; }
@@ -295,7 +317,8 @@ static int pack_wino(bsmi_unet* h, PassSite& p, int ci) {
   for (int part = 0; part < 2; ++part)
     if (pw.res_part_w[part]) { (void)hipFree(pw.res_part_w[part]); pw.res_part_w[part] = nullptr; }
   pw.ready = false;
-  if (!wino_eligible(p, ci)) return BSMI_OK;
+  pw.fused_only = wino_narrow_last(h, p, ci);
+  if (!wino_eligible(p, ci) && !pw.fused_only) return BSMI_OK;
   const HostWeight& wm = h->weights[p.prefix + ".conv_pass." + std::to_string(2 * ci) + ".weight"];
   const HostWeight& wr = h->weights[p.prefix + ".residual.0.weight"];
   const int cin_m = (int)wm.shape[1];
@@ -841,6 +864,7 @@ struct Planner {
     st.use_wino = false;
     const PackedWino& pw = p.wino[ci];
     const bool wants_fused = fuse_up && (ci == 0 || ci == p.nconv - 1);
+    if (pw.fused_only && !fuse_up) return BSMI_OK;  // the upsampling of this pass is not fused: the stage keeps its other form
     const int wm = pw.m, nbatch = wino_batches(wm);
     if (prec != BSMI_PREC_BF16X3 || !pw.ready || (wm == 2 && ((o.H & 1) || (o.W & 1))) || st.use_box || st.use_rh) {
       if (wants_fused) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: the upsampling was fused into this stage, which cannot take the Winograd form", p.prefix.c_str(), ci);
@@ -1210,6 +1234,17 @@ struct Planner {
       st.type = PlanStep::POOL;
       st.in = f_left; st.out = g_in;
       for (int d = 0; d < 3; ++d) st.f[d] = f[d];
+      // Fused pooling (BSMI_POOL_FUSE=0: off): behind an F(4x4) stage a (1,2,2) pool of even extents is stored by the stage's
+      // output transform, whose threads hold whole 4 x 4 tiles (WinoOutArgs::pool) -- the launch that re-read the tensor just
+      // written (0.40 GB for the 300-channel one of the 128^3 block) falls away.  Same bits; the full-resolution tensor is
+      // still written, the skip connection reads it.
+      static const bool pool_fuse = [] { const char* e = getenv("BSMI_POOL_FUSE"); return !(e && e[0] == '0'); }();
+      PlanStep& prod = plan->steps.back();
+      if (pool_fuse && prec == BSMI_PREC_BF16X3 && f[0] == 1 && f[1] == 2 && f[2] == 2 && prod.type == PlanStep::CONV && prod.use_wino &&
+          prod.wino_out.m == 4 && !prod.wino_out.low && prod.wino_out.out == f_left.ptr && !(f_left.H & 1) && !(f_left.W & 1)) {
+        prod.wino_out.pool = g_in.ptr;
+        st.pool_fused = true;
+      }
       plan->steps.push_back(st);
     }
     TDesc g_out;
@@ -1343,7 +1378,7 @@ static int harvest(bsmi_unet* h, Plan* plan) {
       h->prof_ms[ty] += t;
       h->prof_flops[ty] += plan->steps[i].flops;
       if (ty == 1) h->prof_exec += plan->steps[i].exec_flops > 0 ? plan->steps[i].exec_flops : plan->steps[i].flops * (plan->prec == BSMI_PREC_BF16X3 ? 3.0 : 1.0);
-      h->prof_launches[ty] += (plan->fused_first && i < 2) ? 0 : 1;
+      h->prof_launches[ty] += ((plan->fused_first && i < 2) || plan->steps[i].pool_fused) ? 0 : 1;
     }
     plan->spare.push_back(std::move(set));
   }
@@ -1415,6 +1450,11 @@ int get_plan(bsmi_unet* h, int precision, const int64_t in_shape[3], Plan** out)
     plan->fused_first = fp_ready && first_pass_eligible(h) && ps.size() > 3 &&
                         ps[0].type == PlanStep::INPUT && ps[1].type == PlanStep::CONV && ps[2].type == PlanStep::CONV &&
                         ps[1].site == &h->l_conv[0] && ps[2].site == &h->l_conv[0] && ps[2].out.Cpad == 16;
+    if (plan->fused_first && plan->steps[3].type == PlanStep::POOL && plan->steps[3].pool_fused) {
+      // step 2 runs inside first_pass and not as the Winograd stage that would have stored the pooled tensor
+      plan->steps[3].pool_fused = false;
+      plan->steps[2].wino_out.pool = nullptr;
+    }
     // the planner's uploads and fills (hipMemcpy / hipMemsetAsync on the null stream) before any launch on a caller's non-blocking stream
     BSMI_HIP(hipDeviceSynchronize());
     it = h->plans.emplace(key, std::move(plan)).first;
@@ -1799,6 +1839,7 @@ int bsmi_unet_forward(bsmi_unet* h, int precision, const void* raw_dev, int raw_
                          : launch_conv_igemm(st.conv, precision, st.tile, s, h->sk_ws, h->sk_grid);
         break;
       case PlanStep::POOL:
+        if (st.pool_fused) break;  // stored by the output transform of the stage before (Planner::rec, fused pooling)
         rc = launch_maxpool(precision, st.in.ptr, st.out.ptr, st.in.D, st.in.H, st.in.W, st.in.Cpad,
                             st.f[0], st.f[1], st.f[2], s);
         break;

@@ -59,6 +59,9 @@ struct PackedConv {
 struct PackedWino {
   bool ready = false;
   int m = 2;                        // output tile edge: F(2x2, 3x3) or F(4x4, 3x3)
+  // packed only for the fused upsampling (pack_wino: the narrow last stage of a decoder pass): plan_wino takes this form when
+  // the pass runs behind a fused upsampling and leaves the stage to its other forms otherwise
+  bool fused_only = false;
   std::vector<WinoUnit> units;      // K-step list of every batch
   std::vector<int> cin_of_v;        // V channel -> input channel of the concatenated input (-1: pad)
   int Cv = 0;                       // channels of V: every source padded to kChanPad
@@ -137,6 +140,7 @@ struct PlanStep {
   TDesc in, out;
   int f[3], o[3];
   bool skip = false;     // UP step whose map nobody reads: its consumers upsample on the fly (plan_wino, fuse_up)
+  bool pool_fused = false;  // POOL step that launches nothing: the F(4x4) output transform of the step before stores its tensor
   int head = 0;
   double flops = 0;  // algorithmic FLOPs of this launch
   // multiply-adds the matrix pipe is actually given (x 2): tile-padded rows x padded columns x padded K, every batch of a Winograd

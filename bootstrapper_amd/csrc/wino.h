@@ -47,6 +47,11 @@ struct WinoOutArgs {
   int Do, Ty, Tx, Co;
   int relu;
   int m, Ho, Wo;        // m = 2 (0 reads as 2): Ho = 2 Ty, Wo = 2 Tx; m = 4: Ho <= 4 Ty, Wo <= 4 Tx (overhanging tiles are cut)
+  // optional, m = 4 with even Ho and Wo and no `low`: the (1,2,2) max-pool of `out`, split-bf16 [Do][Ho / 2][Wo / 2][Co], stored
+  // by the same launch -- a tile's origin is a multiple of 4, so its 2 x 2 pooled outputs are maxima of values the thread
+  // holds.  The maximum is taken over the values as stored (hi + lo), as unet_ops.hip maxpool_kernel takes it over what it
+  // reads back: the same bits.  `out` is still written whole
+  void* pool;
 };
 
 int launch_wino_in(const WinoInArgs& a, hipStream_t s);

@@ -1,13 +1,14 @@
-// Winograd F(2x2, 3x3) over the in-plane axes of a 3x3x3 "valid" convolution, split-bf16 mode (BSMI_PREC_BF16X3).
+// Winograd F(2x2, 3x3) and F(4x4, 3x3) over the in-plane axes of a 3x3x3 "valid" convolution, split-bf16 mode (BSMI_PREC_BF16X3).
 //
 // out[z][y][x][n] = sum_{kz,ky,kx,c} in[z+kz][y+ky][x+kx][c] w[n][c][kz][ky][kx]   (reference models/3d_affs/unet.py:26-34, a
-// torch.nn.Conv3d) is computed per 2 x 2 in-plane output tile as  Y = A^T [ sum_{kz,c} (G g G^T) . (B^T d B) ] A  with the
-// 4 x 4 input tile d and the kernel plane g = w[n][c][kz]: 16 multiplies per 4 outputs and (kz, c) instead of 36 -- 12 per
-// output instead of 27.  The 16 element-wise products over (kz, c) are 16 independent GEMMs
+// torch.nn.Conv3d) is computed per m x m in-plane output tile as  Y = A^T [ sum_{kz,c} (G g G^T) . (B^T d B) ] A  with the
+// (m + 2) x (m + 2) input tile d and the kernel plane g = w[n][c][kz].  m = 2: 16 multiplies per 4 outputs and (kz, c) instead of
+// 36 -- 12 per output instead of 27; m = 4 (the default of every Winograd stage, second half of this file): 36 per 16 outputs,
+// 6.75 per output.  The (m + 2)^2 element-wise products over (kz, c) are as many independent GEMMs, for m = 2
 //     M[b][m][n] = sum_{kz,c} V[b][z(m)+kz][ty(m)][tx(m)][c] U[b][kz][c][n],      b = 4 xi + nu,
 // i.e. a (3,1,1) convolution of the transformed tensor V[b]: they run as ONE batched launch of the fused split-bf16
 // implicit-GEMM kernel (conv_igemm.hip, ConvArgs::nbatch) with raw f32 sums as its output.  This file holds the two
-// memory-bound transforms around it and the host-side weight transform.
+// memory-bound transforms around it and the host-side weight transform.  F(2x2):
 //   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]   G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]   A^T = [1 1 1 0; 0 1 -1 -1]
 // Arithmetic: d = hi + lo is exact in f32; B^T d B is sums of four such values (f32 rounding, 2^-24); V and U are stored as
 // (hi, lo) bf16 pairs like every operand of this mode (2^-17 per product); M and A^T M A are f32.  Measured against the direct
@@ -606,8 +607,10 @@ __global__ __launch_bounds__(256, 2) void wino4_in_up_kernel(const WinoInArgs a,
   }
 }
 
-// one thread: the 4 x 4 output tile of 4 channels at (z, ty, tx); outputs past (Ho, Wo) -- overhanging tiles -- are not stored
-template <bool LOW>
+// one thread: the 4 x 4 output tile of 4 channels at (z, ty, tx); outputs past (Ho, Wo) -- overhanging tiles -- are not stored.
+// POOL (Ho, Wo even): the thread also stores the tile's 2 x 2 outputs of the (1,2,2) max-pool (WinoOutArgs::pool).  Rows and
+// columns leave the extent in pairs, so a pooled output is stored exactly when its four inputs are.
+template <bool LOW, bool POOL = false>
 __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, size_t total) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -636,6 +639,7 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
 #pragma unroll
   for (int k = 0; k < 4; ++k) bv[k] = a.bias[4 * cg + k];
   uint16_t* out = (uint16_t*)a.out;
+  [[maybe_unused]] float even[4][4];  // POOL: the stored values of the even row of a pair of rows
 #pragma unroll
   for (int p = 0; p < 4; ++p) {
     float in[6][4], y[4][4];
@@ -646,6 +650,7 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
     at4_apply(in, y);
     const int oy = 4 * ty + p;
     if (oy >= a.Ho) continue;
+    [[maybe_unused]] float left[4];   // POOL: the stored values of the even column of a pair, this row
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int ox = 4 * tx + q;
@@ -680,6 +685,27 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
         for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
       }
       store_split4(out, e8, hf, v);
+      if constexpr (POOL) {
+        float sv[4];  // what a reader of `out` gets back: f32(hi) + f32(lo)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float h = __uint_as_float((uint32_t)to_bf16(v[k]) << 16);
+          sv[k] = h + __uint_as_float((uint32_t)to_bf16(v[k] - h) << 16);
+        }
+        if ((p & 1) == 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) even[q][k] = sv[k];
+        } else if ((q & 1) == 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) left[k] = sv[k];
+        } else {
+          float mx[4];   // maxpool_kernel's order: (dy, dx) = (0,0), (0,1), (1,0), (1,1), from -inf
+#pragma unroll
+          for (int k = 0; k < 4; ++k) mx[k] = fmaxf(fmaxf(fmaxf(fmaxf(-INFINITY, even[q > 0 ? q - 1 : 0][k]), even[q][k]), left[k]), sv[k]);
+          const size_t pe = (((size_t)z * (a.Ho >> 1) + (oy >> 1)) * (a.Wo >> 1) + (ox >> 1)) * a.Co + 8 * cv;
+          store_split4((uint16_t*)a.pool, pe, hf, mx);
+        }
+      }
     }
   }
 }
@@ -748,12 +774,14 @@ int launch_wino_out(const WinoOutArgs& a, hipStream_t s) {
   if (a.Do <= 0 || a.Ty <= 0 || a.Tx <= 0 || a.Co % 8) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: bad geometry");
   const int Ho = m == 4 ? a.Ho : 2 * a.Ty, Wo = m == 4 ? a.Wo : 2 * a.Tx;
   if (m == 4 && (Ho < 1 || Wo < 1 || Ho > 4 * a.Ty || Wo > 4 * a.Tx || Ho + 3 < 4 * a.Ty || Wo + 3 < 4 * a.Tx)) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: output extent and F(4x4) tile counts disagree");
+  if (a.pool && (m != 4 || a.low || (Ho & 1) || (Wo & 1))) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: a pooled output needs F(4x4), even extents and no low-resolution residual");
   if (a.low && (a.lf < 1 || a.loz < 0 || a.loz + a.Do > a.lD || a.loy < 0 || a.loy + Ho > a.lH * a.lf || a.lox < 0 || a.lox + Wo > a.lW * a.lf))
     BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: the low-resolution residual does not cover the output");
   const size_t total = (size_t)a.Do * a.Ty * a.Tx * (a.Co / (m == 4 ? 4 : 8));
   const dim3 grid((unsigned)((total + 255) / 256));
   if (m == 4) {
     if (a.low) hipLaunchKernelGGL(wino4_out_kernel<true>, grid, dim3(256), 0, s, a, total);
+    else if (a.pool) hipLaunchKernelGGL((wino4_out_kernel<false, true>), grid, dim3(256), 0, s, a, total);
     else hipLaunchKernelGGL(wino4_out_kernel<false>, grid, dim3(256), 0, s, a, total);
   } else if (a.low) hipLaunchKernelGGL(wino_out_kernel<true>, grid, dim3(256), 0, s, a, total);
   else hipLaunchKernelGGL(wino_out_kernel<false>, grid, dim3(256), 0, s, a, total);

@@ -225,6 +225,14 @@ def _load():
         "bsmi_aug_sample_f32_u8": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
         "bsmi_aug_sample_nearest_i64": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
         "bsmi_aug_sample_nearest_u8": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
+        "bsmi_aug_sample_unit_f32_u8": (i32, [i32, vp, i64p, i64p, i64p, vp, i64p, vp, vp]),
+        "bsmi_aug_noise_f32": (i32, [i32, i64p, vp, C.c_uint64, C.c_float, vp]),
+        "bsmi_aug_section_stats_f32": (i32, [i32, i64p, vp, vp, vp, vp]),
+        "bsmi_aug_intensity_f32": (i32, [i32, i64p, vp, vp, vp, vp, vp]),
+        "bsmi_aug_gamma_f32": (i32, [i32, i64p, vp, vp, vp, vp]),
+        "bsmi_aug_impulse_f32": (i32, [i32, i64p, vp, C.c_uint64, C.c_uint64, vp]),
+        "bsmi_aug_smooth_f32": (i32, [i32, i64p, vp, vp, C.POINTER(C.c_float), i32, vp]),
+        "bsmi_aug_defect_f32": (i32, [i32, i64p, vp, vp, vp, C.c_float, i32, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

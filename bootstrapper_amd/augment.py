@@ -13,8 +13,27 @@ draw.  With I the input shape, c = (I - 1) / 2 and p a voxel index of the input 
 
 Declared differences: E is evaluated at every voxel (the reference's subsample=4 is a CPU shortcut); the 5 % rejection
 test sees the augmented output block (gunpowder's Reject sees the upstream region); rotations are about z only.
-NOT built: the intensity nodes (NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment,
-DefectAugment), the 2-D setups, SyntheticSource, 3-D rotations.
+
+With `intensity` inside the table, raw then runs through the reference's intensity nodes (models/3d_mtlsd/train.py:117-132
+and its siblings) on the device, one launch of csrc/augment_intensity.hip per node, in the reference's order: NoiseAugment
+-> IntensityAugment -> GammaAugment -> ImpulseNoiseAugment -> SmoothAugment -> DefectAugment.  These too are specified rules
+(restated in float64 by tests/intensity_ref.py): gunpowder and skimage are not installed where this
+was written, so parity is in distribution.  x is raw in [0, 1], sections are the z planes:
+
+    resample   the trilinear expression above, written v / 255
+    noise      x = clip(x + sqrt(noise_var) n), n a standard normal per voxel (Philox4x32-10 on the device)
+    intensity  x = clip(m_z + (x - m_z) scale_z + shift_z), m_z the section's mean
+    gamma      x = ((x - a) / (b - a))^g_z (b - a) + a with a, b the section's extrema, where b - a > 1e-3
+    impulse    a voxel is replaced with probability q by a value in U[0, 1)
+    smooth     scipy.ndimage.gaussian_filter(x, sigma) over all three axes: radius int(4 sigma + 0.5), border reflect
+    defect     per section: 0 or 1 throughout (prob_missing), or x = m + (x - m) contrast_scale (prob_low_contrast)
+    output     2 x - 1
+
+Declared quirk: the reference's ImpulseNoiseAugment draws its locations with the node's p, not with the pixel_p its call
+site passes (gp/impulse_noise_augment.py:58), so the default of `impulse_pixel_p` is q = impulse_p, what the reference
+executes; setting the key gives the documented 0.05 or any other value.
+NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, the 2-D setups,
+SyntheticSource, 3-D rotations.
 """
 import ctypes as C
 import dataclasses
@@ -22,15 +41,75 @@ import math
 
 import numpy as np
 
+# what the trainer's log line names as missing: without `intensity`, and with it
 NOT_BUILT = "NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw"
+NOT_BUILT_WITH_INTENSITY = "DefectAugment's deformation and artifacts; augmentation of the 2-D setups and of synthetic labels"
 MAX_LATTICE_NODES = 4096   # csrc/augment.hip: 48 KiB of offsets in LDS
+MAX_RADIUS = 6             # csrc/augment_intensity.hip: taps of the smoothing kernel, int(4 sigma + 0.5)
+STAT_PARTS = 16            # include/bsmi.h: BSMI_AUG_STAT_PARTS
+
+
+@dataclasses.dataclass(frozen=True)
+class IntensityParams:
+    """The arguments of the six intensity nodes; the defaults are the reference's call site (models/3d_mtlsd/train.py:117-132).
+    impulse_pixel_p: the share of voxels an applied ImpulseNoiseAugment replaces.  None (the default) is what the reference
+    EXECUTES, impulse_p: its node draws the locations with p, not with the pixel_p = 0.05 its call site passes.  Set the
+    key to get the documented 0.05."""
+    noise_p: float = 0.5
+    noise_var: float = 0.01
+    intensity_p: float = 0.5
+    scale: tuple = (0.9, 1.1)
+    shift: tuple = (-0.1, 0.1)
+    gamma_p: float = 0.5
+    gamma: tuple = (0.8, 1.2)
+    impulse_p: float = 0.5
+    impulse_pixel_p: float = None
+    smooth_p: float = 0.5
+    blur: tuple = (0.5, 1.5)
+    prob_missing: float = 0.1
+    prob_low_contrast: float = 0.1
+    contrast_scale: float = 0.1
+
+    @classmethod
+    def from_config(cls, value):
+        """The key `intensity` of the `[augment]` table: absent / false -> None, true -> the defaults, a table -> overrides."""
+        if value is None or value is False:
+            return None
+        if value is True:
+            return cls()
+        if not isinstance(value, dict):
+            raise ValueError(f"augment.intensity must be true, false or a table, not {value!r}")
+        names = [f.name for f in dataclasses.fields(cls)]
+        unknown = sorted(set(value) - set(names))
+        if unknown:
+            raise ValueError(f"unknown augment.intensity key(s) {', '.join(unknown)}; known: {', '.join(names)}")
+        kw = {}
+        for k, v in value.items():
+            if k in ("scale", "shift", "gamma", "blur"):
+                kw[k] = tuple(float(x) for x in v)
+                if len(kw[k]) != 2 or not kw[k][0] <= kw[k][1] or (k != "shift" and kw[k][0] <= 0):
+                    raise ValueError(f"augment.intensity.{k} {v!r}: two numbers, low <= high" + ("" if k == "shift" else ", positive"))
+                if k == "blur" and int(4.0 * kw[k][1] + 0.5) > MAX_RADIUS:
+                    raise ValueError(f"augment.intensity.blur {v!r}: sigma below {(MAX_RADIUS + 0.5) / 4} (a radius int(4 sigma + 0.5) of at most {MAX_RADIUS})")
+            else:
+                kw[k] = float(v)
+                if k in ("noise_var", "contrast_scale"):
+                    if kw[k] < 0:
+                        raise ValueError(f"augment.intensity.{k} {v!r}: not negative")
+                elif kw[k] < 0 or kw[k] > 1:
+                    raise ValueError(f"augment.intensity.{k} {v!r}: a probability")
+        p = cls(**kw)
+        if p.prob_missing + p.prob_low_contrast > 1:
+            raise ValueError("augment.intensity: prob_missing + prob_low_contrast exceeds 1")
+        return p
 
 
 @dataclasses.dataclass(frozen=True)
 class AugParams:
     """The arguments of the three nodes; the defaults are the reference's (models/3d_affs/train.py:95-104).
     control_point_spacing / jitter_sigma: world units per axis, None = the reference's voxel_size * (vs[2], vs[0], vs[0])
-    and voxel_size * 2."""
+    and voxel_size * 2.  intensity: an IntensityParams turns on the intensity chain of raw; None (the default, also of
+    `augment = true`): the geometric chain alone."""
     simple: bool = True
     deform_p: float = 0.5
     scale_interval: tuple = (0.9, 1.1)
@@ -41,6 +120,7 @@ class AugParams:
     prob_slip: float = 0.2
     prob_shift: float = 0.2
     shift_sigma: float = 3.0
+    intensity: IntensityParams = None
 
     @classmethod
     def from_config(cls, value):
@@ -57,7 +137,9 @@ class AugParams:
             raise ValueError(f"unknown augment key(s) {', '.join(unknown)}; known: {', '.join(names)}")
         kw = {}
         for k, v in value.items():
-            if k in ("simple", "rotate"):
+            if k == "intensity":
+                kw[k] = IntensityParams.from_config(v)
+            elif k in ("simple", "rotate"):
                 kw[k] = bool(v)
             elif k == "scale_interval":
                 kw[k] = tuple(float(x) for x in v)
@@ -157,6 +239,93 @@ def draw_plan(rng, params, shape, voxel_size):
         slip = np.rint(rng.normal(0.0, params.shift_sigma, (d, 2)))
         total = np.cumsum(step * on[:, None], axis=0) + slip * slip_on[:, None]
         plan.shifts = np.ascontiguousarray(total.T).astype(np.int32)
+    return plan
+
+
+@dataclasses.dataclass
+class IntensityPlan:
+    """One sample's intensity draws, in the number formats the kernels read.  A node that is not applied holds None.
+    noise_sigma: float32 sqrt(noise_var).  scale, shift, gamma: float32 [D], per section (gamma already mapped to the
+    exponent).  impulse_threshold: floor(q * 2^32), an int in [0, 2^32].  blur: the sigma drawn; weights: float32
+    [2 radius + 1], the normalised taps.  defect: int32 [D] of 0 (unchanged), 1 / 2 (missing: the section becomes 0 / 1),
+    3 (low contrast), or None where no section has a defect.  seed: the 64-bit Philox key of noise and impulse."""
+    shape: tuple
+    noise_sigma: float = None
+    scale: np.ndarray = None
+    shift: np.ndarray = None
+    gamma: np.ndarray = None
+    impulse_threshold: int = None
+    blur: float = None
+    weights: np.ndarray = None
+    defect: np.ndarray = None
+    contrast_scale: float = 0.1
+    seed: int = 0
+
+    @property
+    def applied(self):
+        """whether any node changes raw; if none does, the source takes today's sample_raw path"""
+        return any(v is not None for v in (self.noise_sigma, self.scale, self.gamma, self.impulse_threshold, self.weights, self.defect))
+
+
+def gamma_interval(gamma):
+    """GammaAugment's draw interval: (lo', hi') with v' = (max(v, 1 / v) - 1) * (-1 if v < 1 else 1)"""
+    return tuple((max(v, 1.0 / v) - 1.0) * (-1.0 if v < 1 else 1.0) for v in gamma)
+
+
+def gamma_exponent(g):
+    """a draw of gamma_interval -> the exponent: 1 / (1 - g) below 0, else g + 1"""
+    g = np.asarray(g, dtype=np.float64)
+    return np.where(g < 0, 1.0 / (1.0 - np.minimum(g, 0.0)), g + 1.0)
+
+
+def gaussian_weights(sigma):
+    """scipy.ndimage's taps for truncate = 4: radius int(4 sigma + 0.5), exp(-x^2 / (2 sigma^2)) normalised in float64, as float32"""
+    radius = int(4.0 * float(sigma) + 0.5)
+    if radius > MAX_RADIUS:
+        raise ValueError(f"smoothing sigma {sigma}: a radius of {radius}, at most {MAX_RADIUS}")
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x * x)
+    return (w / w.sum()).astype(np.float32)
+
+
+def draw_intensity_plan(rng, params, shape):
+    """One intensity plan for a block of `shape` (D sections), every draw taken from `rng` in this order; a node whose
+    probability is 0 takes no draw at all.
+      1. noise:     rng.random() < noise_p
+      2. intensity: rng.random() < intensity_p; if applied: rng.uniform(*scale, D), then rng.uniform(*shift, D)
+      3. gamma:     rng.random() < gamma_p; if applied: rng.uniform(*gamma_interval(gamma), D), mapped by gamma_exponent
+      4. impulse:   rng.random() < impulse_p
+      5. smooth:    rng.random() < smooth_p; if applied: sigma = rng.uniform(*blur)
+      6. defect:    if prob_missing + prob_low_contrast > 0: r = rng.random(D), then rng.random(D) < 0.5 -- the value, 0 or
+                    1, a section takes if it is missing; both always, so that the stream does not depend on the outcome
+      7. seed:      if noise or impulse is applied: rng.integers(0, 2^64, dtype=uint64), the Philox key of both
+    """
+    shape = tuple(int(v) for v in shape)
+    d = shape[0]
+    plan = IntensityPlan(shape, contrast_scale=float(params.contrast_scale))
+    if params.noise_p > 0 and rng.random() < params.noise_p:
+        plan.noise_sigma = float(np.float32(math.sqrt(params.noise_var)))
+    if params.intensity_p > 0 and rng.random() < params.intensity_p:
+        plan.scale = rng.uniform(*params.scale, d).astype(np.float32)
+        plan.shift = rng.uniform(*params.shift, d).astype(np.float32)
+    if params.gamma_p > 0 and rng.random() < params.gamma_p:
+        plan.gamma = gamma_exponent(rng.uniform(*gamma_interval(params.gamma), d)).astype(np.float32)
+    if params.impulse_p > 0 and rng.random() < params.impulse_p:
+        q = params.impulse_p if params.impulse_pixel_p is None else params.impulse_pixel_p
+        plan.impulse_threshold = int(math.floor(q * 2.0 ** 32))
+    if params.smooth_p > 0 and rng.random() < params.smooth_p:
+        plan.blur = float(rng.uniform(*params.blur))
+        plan.weights = gaussian_weights(plan.blur)
+    if params.prob_missing + params.prob_low_contrast > 0:
+        r = rng.random(d)
+        missing = r < params.prob_missing
+        low = ~missing & (r < params.prob_missing + params.prob_low_contrast)
+        mode = np.where(low, 3, 0).astype(np.int32)
+        mode[missing] = np.where(rng.random(d) < 0.5, 1, 2)[missing]
+        if mode.any():
+            plan.defect = mode
+    if plan.noise_sigma is not None or plan.impulse_threshold is not None:
+        plan.seed = int(rng.integers(0, 2 ** 64, dtype=np.uint64))
     return plan
 
 
@@ -267,3 +436,140 @@ def sample_mask(coords_dev, crop, region=None):
     """uint8 crop -> uint8 region: nearest, as the labels"""
     import torch
     return _sample("bsmi_aug_sample_nearest_u8", coords_dev, crop, region, torch.uint8, torch.uint8)
+
+
+def sample_unit(coords_dev, crop, region=None):
+    """uint8 crop -> float32 region in [0, 1]: trilinear, v / 255 -- what the intensity chain starts from"""
+    import torch
+    return _sample("bsmi_aug_sample_unit_f32_u8", coords_dev, crop, region, torch.uint8, torch.float32)
+
+
+# ---- the intensity nodes: each changes a contiguous float32 CUDA block (D, H, W) in [0, 1] in place ----
+
+def _block(x):
+    import torch
+    from . import _lib
+    if x.dtype != torch.float32 or x.dim() != 3 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("the block must be a contiguous float32 CUDA tensor (D, H, W)")
+    return x.device.index, _lib.i64x3(x.shape), C.c_void_p(x.data_ptr()), C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def _per_section(x, values, dtype, what):
+    """`values` (numpy or tensor, one per section) as a tensor of `dtype` on x's device"""
+    import torch
+    t = values if isinstance(values, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(values)).to(x.device)
+    if t.dtype != dtype or tuple(t.shape) != (x.shape[0],) or t.device != x.device or not t.is_contiguous():
+        raise ValueError(f"{what}: one {dtype} value per section ({x.shape[0]}) on the block's device")
+    t.record_stream(torch.cuda.current_stream(x.device))
+    return t
+
+
+def noise(x, seed, sigma):
+    """x = clip(x + sigma n), n from words 0 and 1 of Philox4x32-10(counter = voxel index, key = seed)"""
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    _lib.check(_lib.lib.bsmi_aug_noise_f32(dev, shape, ptr, C.c_uint64(int(seed)), C.c_float(float(sigma)), stream))
+    return x
+
+
+def impulse(x, seed, threshold):
+    """a voxel whose Philox word 2 < threshold (an int in [0, 2^32]) becomes (word 3 >> 8) * 2^-24"""
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    _lib.check(_lib.lib.bsmi_aug_impulse_f32(dev, shape, ptr, C.c_uint64(int(seed)), C.c_uint64(int(threshold)), stream))
+    return x
+
+
+def section_stats(x):
+    """float32 CUDA (D, 3): mean, min and max of every section, reduced in a fixed order (one block, one result)"""
+    import torch
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    partials = torch.empty((x.shape[0], STAT_PARTS, 3), dtype=torch.float32, device=x.device)
+    stats = torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib.bsmi_aug_section_stats_f32(dev, shape, ptr, C.c_void_p(partials.data_ptr()), C.c_void_p(stats.data_ptr()), stream))
+    return stats
+
+
+def _stats(x, stats):
+    import torch
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (x.shape[0], 3) or stats.device != x.device or not stats.is_contiguous():
+        raise ValueError("stats must be section_stats of the block: float32 (D, 3) on its device")
+    return C.c_void_p(stats.data_ptr())
+
+
+def intensity(x, stats, scale, shift):
+    """x = clip(m_z + (x - m_z) scale_z + shift_z) with m_z = stats[z, 0]"""
+    import torch
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    sc, sh = _per_section(x, scale, torch.float32, "scale"), _per_section(x, shift, torch.float32, "shift")
+    _lib.check(_lib.lib.bsmi_aug_intensity_f32(dev, shape, ptr, _stats(x, stats), C.c_void_p(sc.data_ptr()), C.c_void_p(sh.data_ptr()), stream))
+    return x
+
+
+def gamma(x, stats, exponent):
+    """x = ((x - a) / (b - a))^g_z (b - a) + a with (a, b) = stats[z, 1:], where b - a > 1e-3"""
+    import torch
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    g = _per_section(x, exponent, torch.float32, "gamma")
+    _lib.check(_lib.lib.bsmi_aug_gamma_f32(dev, shape, ptr, _stats(x, stats), C.c_void_p(g.data_ptr()), stream))
+    return x
+
+
+def smooth(x, weights):
+    """the separable Gaussian of `weights` (float32, 2 radius + 1 normalised taps: gaussian_weights) along z, y, x, border reflect"""
+    import torch
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.ndim != 1 or w.size % 2 != 1:
+        raise ValueError("weights: 2 radius + 1 taps")
+    tmp = torch.empty_like(x)
+    _lib.check(_lib.lib.bsmi_aug_smooth_f32(dev, shape, ptr, C.c_void_p(tmp.data_ptr()), _f32(w), w.size // 2, stream))
+    return x
+
+
+def defect(x, stats, mode, contrast_scale, final_map=False):
+    """per section mode 0: unchanged, 1 / 2: all 0 / all 1, 3: x = m_z + (x - m_z) contrast_scale; mode None: no section;
+    final_map: then x = 2 x - 1"""
+    import torch
+    from . import _lib
+    dev, shape, ptr, stream = _block(x)
+    m = _per_section(x, mode, torch.int32, "defect mode") if mode is not None else None
+    _lib.check(_lib.lib.bsmi_aug_defect_f32(dev, shape, ptr, _stats(x, stats) if m is not None else None,
+                                            C.c_void_p(m.data_ptr()) if m is not None else None, C.c_float(float(contrast_scale)), 1 if final_map else 0, stream))
+    return x
+
+
+def apply_intensity(x, plan, final_map=True):
+    """The chain of `plan` (an IntensityPlan) on x in [0, 1], in place, a launch per applied node and the section statistics
+    its successor needs; then 2 x - 1.  A node the plan skips is not launched, so it leaves the values bit-equal."""
+    if tuple(x.shape) != tuple(plan.shape):
+        raise ValueError(f"block of shape {tuple(x.shape)} for a plan of {plan.shape}")
+    if plan.noise_sigma is not None:
+        noise(x, plan.seed, plan.noise_sigma)
+    if plan.scale is not None:
+        intensity(x, section_stats(x), plan.scale, plan.shift)
+    if plan.gamma is not None:
+        gamma(x, section_stats(x), plan.gamma)
+    if plan.impulse_threshold is not None:
+        impulse(x, plan.seed, plan.impulse_threshold)
+    if plan.weights is not None:
+        smooth(x, plan.weights)
+    low = plan.defect is not None and bool((plan.defect == 3).any())
+    return defect(x, section_stats(x) if low else _no_stats(x), plan.defect, plan.contrast_scale, final_map)
+
+
+def _no_stats(x):
+    """stats no section reads (no low-contrast section in the plan): allocated, never reduced"""
+    import torch
+    return torch.empty((x.shape[0], 3), dtype=torch.float32, device=x.device)
+
+
+def sample_raw_intensity(coords_dev, crop, plan):
+    """uint8 crop -> float32 block in [-1, 1] through the intensity chain; a plan that applies no node: sample_raw, bit for bit"""
+    if plan is None or not plan.applied:
+        return sample_raw(coords_dev, crop)
+    return apply_intensity(sample_unit(coords_dev, crop), plan)

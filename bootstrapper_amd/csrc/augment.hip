@@ -117,7 +117,9 @@ __global__ __launch_bounds__(256) void aug_sample_nearest_kernel(AugRegion g, co
   }
 }
 
-// trilinear on u8, written as (v * 2 - 255) / 255 (Normalize + IntensityScaleShift(2, -1)); both cell corners clamped to the crop
+// trilinear on u8, written as (v * 2 - 255) / 255 (Normalize + IntensityScaleShift(2, -1)); both cell corners clamped to the crop.
+// kUnit: v / 255 instead (Normalize alone), what the intensity chain of augment_intensity.hip starts from
+template <bool kUnit>
 __global__ __launch_bounds__(256) void aug_sample_f32_u8_kernel(AugRegion g, const float* __restrict__ coords, const uint8_t* __restrict__ crop,
                                                                 float* __restrict__ out) {
   const uint32_t total = (uint32_t)g.rd * g.rh * g.rw;  // fewer than 2^31 voxels
@@ -139,7 +141,10 @@ __global__ __launch_bounds__(256) void aug_sample_f32_u8_kernel(AugRegion g, con
     const float c00 = lerp((float)r00[x0], (float)r00[x1], fx), c01 = lerp((float)r01[x0], (float)r01[x1], fx);
     const float c10 = lerp((float)r10[x0], (float)r10[x1], fx), c11 = lerp((float)r11[x0], (float)r11[x1], fx);
     const float v = lerp(lerp(c00, c01, fy), lerp(c10, c11, fy), fz);
-    out[idx] = (v * 2.0f - 255.0f) / 255.0f;  // on a voxel centre the numerator is exact: half an ulp of v * 2 / 255 - 1
+    if constexpr (kUnit)
+      out[idx] = v / 255.0f;
+    else
+      out[idx] = (v * 2.0f - 255.0f) / 255.0f;  // on a voxel centre the numerator is exact: half an ulp of v * 2 / 255 - 1
   }
 }
 
@@ -230,7 +235,12 @@ int bsmi_aug_coords(int device, const int64_t shape[3], const float linear[5], c
 
 int bsmi_aug_sample_f32_u8(int device, const float* coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
                            const int64_t region_shape[3], const uint8_t* crop_dev, const int64_t crop_shape[3], float* out_dev, void* stream) {
-  return sample(device, aug_sample_f32_u8_kernel, coords_dev, coords_shape, region_offset, region_shape, crop_dev, crop_shape, out_dev, stream);
+  return sample(device, aug_sample_f32_u8_kernel<false>, coords_dev, coords_shape, region_offset, region_shape, crop_dev, crop_shape, out_dev, stream);
+}
+
+int bsmi_aug_sample_unit_f32_u8(int device, const float* coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
+                                const int64_t region_shape[3], const uint8_t* crop_dev, const int64_t crop_shape[3], float* out_dev, void* stream) {
+  return sample(device, aug_sample_f32_u8_kernel<true>, coords_dev, coords_shape, region_offset, region_shape, crop_dev, crop_shape, out_dev, stream);
 }
 
 int bsmi_aug_sample_nearest_i64(int device, const float* coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],

@@ -5,14 +5,15 @@ Reference being mirrored (paths relative to /root/reference/bootstrapper):
   models/3d_affs/train.py:160-199 train(setup_dir, voxel_size, max_iterations, samples, save_checkpoints_every, ...)
   training.py:96-137              fit(): seed 42, checkpoints `model_checkpoint_<step>`, resume from the latest one
 
-What is NOT restated: the intensity nodes of the gunpowder chain of models/3d_affs/train.py:105-120 (noise / intensity /
-gamma / impulse / smooth / defect augmentations) and the snapshot callback -- third-party pipeline code outside the hot
-path.  `SampleSource` does the deterministic part: random location with the >= 5 % labelled-voxel rejection, Normalize +
+What is NOT restated: DefectAugment's deformation and artifacts, and the snapshot callback -- third-party pipeline code
+outside the hot path.  `SampleSource` does the deterministic part: random location with the >= 5 % labelled-voxel rejection, Normalize +
 IntensityScaleShift(2, -1), then GrowBoundary, AddAffinities on the configured neighbourhood and BalanceLabels in one
 device call (`affinity_targets`).  With the train config key `augment` it also applies the geometric chain of
 models/3d_affs/train.py:95-104 (SimpleAugment -> DeformAugment -> ShiftAugment) on the device, as one coordinate map
-(augment.py, csrc/augment.hip; specified rules); without the key the batches are un-augmented
-crops, as before.  `SectionSource`
+(augment.py, csrc/augment.hip; specified rules), and with `intensity` inside that table the
+intensity nodes of models/3d_affs/train.py:105-120 on raw (noise / intensity / gamma / impulse / smooth / defect: a launch
+per node, csrc/augment_intensity.hip; specified rules, section 7k); without the key the batches are un-augmented crops,
+as before.  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
 of each section in one launch each (csrc/train2d.hip).  `SyntheticSource` feeds the second-stage setups
 (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
@@ -317,7 +318,8 @@ class SampleSource:
     def __init__(self, samples, input_shape, output_shape, neighborhood, device=0, seed=42, head="affs", grow_boundary=0,
                  lsd_sigma=None, lsd_downsample=1, voxel_size=(1, 1, 1), augment=None):
         """augment: an augment.AugParams (or True for the reference's arguments) turns on the geometric chain SimpleAugment ->
-        DeformAugment -> ShiftAugment (augment.py); None: un-augmented crops, the same batches as without the argument."""
+        DeformAugment -> ShiftAugment (augment.py), and with its field `intensity` set the intensity chain of raw after it;
+        None: un-augmented crops, the same batches as without the argument."""
         self.samples = [(open_ds(s["raw"]), open_ds(s["labels"]), open_ds(s["mask"]) if s.get("mask") else None) for s in samples]
         self.inp, self.out = tuple(input_shape), tuple(output_shape)
         self.nhood = [list(map(int, o)) for o in neighborhood]
@@ -378,7 +380,9 @@ class SampleSource:
         """One batch through the geometric chain: location and plan drawn from self.rng (location first, then
         augment.draw_plan's order), one crop of raw, labels and mask -- augment.source_box of the plan, zeros beyond the
         volume -- uploaded, one coordinate launch, one resampling launch per array, the usual targets on the augmented
-        labels and mask.  The 5 % test sees the augmented output block; a failing draw is redrawn, location and plan."""
+        labels and mask.  The 5 % test sees the augmented output block; a failing draw is redrawn, location and plan.
+        With augment.intensity, the accepted attempt then draws its intensity plan (augment.draw_intensity_plan's order) and
+        raw runs through the intensity chain; a plan that applies no node takes today's resampling launch."""
         from . import augment as aug
         ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
         cv = self._lsd_context()
@@ -409,7 +413,9 @@ class SampleSource:
             if float(unl_dev.float().mean()) < 0.05:   # gp.Reject(mask=unlabelled, min_masked=0.05), on the augmented block
                 continue
             raw_crop = torch.from_numpy(self._read_padded(raw_ds, start, size, np.uint8)).to(self.dev)
-            batch = {"raw": aug.sample_raw(coords, raw_crop)}
+            # the intensity draws come after the test has accepted the attempt: a rejected one takes none of them
+            iplan = aug.draw_intensity_plan(self.rng, self.augment.intensity, self.inp) if self.augment.intensity is not None else None
+            batch = {"raw": aug.sample_raw_intensity(coords, raw_crop, iplan)}
             if self.head != "affs":
                 sig = [float(self.lsd_sigma)] * 3 if isinstance(self.lsd_sigma, (int, float)) else list(self.lsd_sigma)
                 lsds, lw = lsd_targets(big, cv, self.out, sig, self.voxel_size, self.lsd_df, bun)
@@ -754,8 +760,15 @@ def run_training(config_file, device=0, batches=None, log=print):
         log(f"optimizer state restored (step {trainer.step_count()})")
     if batches is None:
         if config.get("augment"):
-            from .augment import NOT_BUILT
-            log(f"note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`); not built: {NOT_BUILT}")
+            from .augment import NOT_BUILT, NOT_BUILT_WITH_INTENSITY, AugParams
+            params = AugParams.from_config(config["augment"])
+            if params.intensity is not None:
+                log("note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`) and the intensity "
+                    "chain of raw (NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment, DefectAugment: "
+                    f"`augment.intensity`); not built: {NOT_BUILT_WITH_INTENSITY}")
+            else:
+                log(f"note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`); not built: {NOT_BUILT} "
+                    "(`intensity = true` inside the `[augment]` table turns them on)")
         else:
             log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
                 "(`augment = true` turns on the geometric chain of the 3-D setups)")

@@ -852,6 +852,45 @@ int bsmi_aug_sample_nearest_u8(int device, const float *coords_dev, const int64_
                                const int64_t region_shape[3], const uint8_t *crop_dev, const int64_t crop_shape[3], uint8_t *out_dev,
                                void *stream);
 
+/* ---- training augmentation: the intensity chain of raw (csrc/augment_intensity.hip; reference models/3d_mtlsd/train.py:
+ * 117-132: NoiseAugment -> IntensityAugment -> GammaAugment -> ImpulseNoiseAugment -> SmoothAugment -> DefectAugment; the
+ * rules in full: DESIGN.md section 7k, tests/intensity_ref.py) ----
+ * Specified rules, like the geometric chain: parity with gunpowder / skimage is in distribution.  Each node is one call on
+ * a float32 block x_dev [D][H][W] with values in [0, 1], changed in place; a node the caller's plan skips is simply not
+ * called.  Sections are the z planes.  Stateless, asynchronous on `stream`; fewer than 2^31 voxels, at most 65535 sections.
+ *
+ *   sample_unit_f32_u8   aug_sample_f32_u8 with out = v / 255 (one rounded division): the chain's input.
+ *   noise      x = clip(x + sigma * n, 0, 1), n a standard normal per voxel (below).
+ *   section_stats  stats_dev [D][3] = (mean, min, max) of every section.  Deterministic: BSMI_AUG_STAT_PARTS workgroups per
+ *              section each reduce a fixed chunk in a fixed order into partials_dev (workspace, [D][BSMI_AUG_STAT_PARTS][3]
+ *              floats), which a second launch combines in index order; mean = sum / (H * W).  No atomics.
+ *   intensity  x = clip(m_z + (x - m_z) * scale_z + shift_z, 0, 1); m_z = stats[z][0]; scale_dev, shift_dev: float32 [D].
+ *   gamma      with a = stats[z][1], b = stats[z][2]: where b - a > 1e-3, x = ((x - a) / (b - a))^gamma_z * (b - a) + a, held to
+ *              [a, b]; x = a stays a; otherwise the section is unchanged.  gamma_dev: float32 [D], positive.
+ *   impulse    a voxel whose word o2 < threshold (threshold <= 2^32; 2^32: every voxel) becomes (o3 >> 8) * 2^-24.
+ *   smooth     separable Gaussian with the caller's normalised taps weights[2 * radius + 1] (host memory), radius <=
+ *              BSMI_AUG_MAX_RADIUS, border "reflect" (d c b a | a b c d, repeated where the radius exceeds the axis), passes
+ *              along z (x_dev -> tmp_dev, a workspace of the block's size), then y and x (one launch, from a tile staged
+ *              with its halo in LDS, tmp_dev -> x_dev); each tap sum runs from tap 0 upwards.
+ *   defect     mode_dev int32 [D] or NULL: 0 unchanged, 1 / 2 the section becomes 0 / 1, 3 x = m_z + (x - m_z) * contrast_scale;
+ *              then, if final_map, x = 2 x - 1 (the chain's output).
+ * Per-voxel random numbers: one Philox4x32-10 call per voxel, key (seed low word, seed high word), counter (linear voxel
+ * index, 0, 0, 0), output o0 .. o3; u1 = ((o0 >> 8) + 1) * 2^-24, u2 = (o1 >> 8) * 2^-24, n = sqrt(-2 ln u1) * cospi(2 u2). */
+#define BSMI_AUG_STAT_PARTS 16
+#define BSMI_AUG_MAX_RADIUS 6
+int bsmi_aug_sample_unit_f32_u8(int device, const float *coords_dev, const int64_t coords_shape[3], const int64_t region_offset[3],
+                                const int64_t region_shape[3], const uint8_t *crop_dev, const int64_t crop_shape[3], float *out_dev,
+                                void *stream);
+int bsmi_aug_noise_f32(int device, const int64_t shape[3], float *x_dev, uint64_t seed, float sigma, void *stream);
+int bsmi_aug_section_stats_f32(int device, const int64_t shape[3], const float *x_dev, float *partials_dev, float *stats_dev, void *stream);
+int bsmi_aug_intensity_f32(int device, const int64_t shape[3], float *x_dev, const float *stats_dev, const float *scale_dev,
+                           const float *shift_dev, void *stream);
+int bsmi_aug_gamma_f32(int device, const int64_t shape[3], float *x_dev, const float *stats_dev, const float *gamma_dev, void *stream);
+int bsmi_aug_impulse_f32(int device, const int64_t shape[3], float *x_dev, uint64_t seed, uint64_t threshold, void *stream);
+int bsmi_aug_smooth_f32(int device, const int64_t shape[3], float *x_dev, float *tmp_dev, const float *weights, int radius, void *stream);
+int bsmi_aug_defect_f32(int device, const int64_t shape[3], float *x_dev, const float *stats_dev, const int32_t *mode_dev,
+                        float contrast_scale, int final_map, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

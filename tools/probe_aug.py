@@ -1,11 +1,15 @@
-"""Dev tool: the geometric training augmentation on one GPU -> JSON lines.
+"""Dev tool: the training augmentation, geometric and intensity, on one GPU -> JSON lines.
 
 launches device-event ms of each launch (after a warm-up, median of 9) at the 3d_mtlsd shape, input (32, 196, 196), output
          (4, 104, 104): aug_coords for a full plan (lattice + shifts), raw over the input block, labels and mask over the
-         output block grown by the LSD context; with the bytes each launch must move and the rate that makes.
-source   batches/s of SampleSource alone on a synthetic Zarr store written here, with and without `augment`, wall clock.
-train    steps/s of a Trainer of the same setup fed through PrefetchSource, with and without `augment`, alternating, and
-         how long the trainer waited for batches in each.
+         output block grown by the LSD context; with the bytes each launch must move and the rate that makes.  Then a leg
+         per launch of the intensity chain on the input block: unit resampling, noise, section statistics (its two
+         launches), intensity, gamma, impulse, smooth (z pass and y/x pass together, sigma 1.5), defect, and the whole
+         chain of a plan that applies every node.
+source   batches/s of SampleSource alone on a synthetic Zarr store written here: plain, `augment`, `augment` with
+         `intensity`, wall clock.
+train    steps/s of a Trainer of the same setup fed through PrefetchSource with each of the three, alternating, and how long
+         the trainer waited for batches in each.
 The store is at voxel size (40, 8, 8) with an LSD sigma of 80: at (40, 4, 4) the descriptors' context (60 voxels) exceeds the
 network's (46), which the augmented source refuses.  `--only launches|source|train`; `--batches N` (default 40)."""
 import argparse, json, os, sys, tempfile, time
@@ -56,6 +60,26 @@ def launches_part():
     # bytes a launch cannot avoid: the coordinate planes, one gather per corner or sample (counted at its own size, not the
     # sector it drags in), the output.  coords also includes its two small uploads (lattice, shifts) in the timed call.
     need = {"coords": 12 * n_in, "raw": (12 + 8 + 4) * n_in, "labels": (12 + 8 + 8) * n_reg, "mask": (12 + 1 + 1) * n_reg}
+    # the intensity chain: every node on the input block, in place (values stay in [0, 1] whatever the repeat count)
+    x = A.sample_unit(coords, raw)
+    d = INPUT[0]
+    sec = np.random.default_rng(1)
+    scale, shift = [torch.from_numpy(sec.uniform(lo_, hi_, d).astype(np.float32)).cuda() for lo_, hi_ in ((0.9, 1.1), (-0.1, 0.1))]
+    expo = torch.from_numpy(sec.uniform(0.8, 1.2, d).astype(np.float32)).cuda()
+    mode = torch.from_numpy((np.arange(d) % 4).astype(np.int32)).cuda()
+    weights = A.gaussian_weights(1.5)
+    st = A.section_stats(x)
+    full = A.IntensityPlan(INPUT, noise_sigma=0.1, scale=scale.cpu().numpy(), shift=shift.cpu().numpy(), gamma=expo.cpu().numpy(),
+                           impulse_threshold=2 ** 31, blur=1.5, weights=weights, defect=mode.cpu().numpy(), seed=7)
+    ims = {"unit": events(lambda: A.sample_unit(coords, raw)), "noise": events(lambda: A.noise(x, 7, 0.1)),
+           "stats": events(lambda: A.section_stats(x)), "intensity": events(lambda: A.intensity(x, st, scale, shift)),
+           "gamma": events(lambda: A.gamma(x, st, expo)), "impulse": events(lambda: A.impulse(x, 7, 2 ** 31)),
+           "smooth": events(lambda: A.smooth(x, weights)), "defect": events(lambda: A.defect(x, st, mode, 0.1, True)),
+           "chain": events(lambda: A.apply_intensity(x, full, final_map=False))}
+    ms.update({"intensity_" + k: v for k, v in ims.items()})
+    # read + write of the block; stats reads it once; smooth reads and writes it twice; the chain: 3 statistics and 7 passes
+    need.update({"intensity_" + k: v * n_in for k, v in {"unit": 12 + 8 + 4, "noise": 8, "stats": 4, "intensity": 8, "gamma": 8, "impulse": 8,
+                                                           "smooth": 16, "defect": 8, "chain": 3 * 4 + 7 * 8}.items()})
     return {"part": "launches", "crop": list(size), "lattice": list(plan.lattice.shape[1:]), "region": region[1], "ms": ms,
             "needed_MB": {k: v / 1e6 for k, v in need.items()}, "GB_per_s": {k: need[k] / ms[k] / 1e6 for k in ms}}
 
@@ -75,7 +99,7 @@ def write_store(root):
 
 def source_part(cfg, batches):
     res = {"part": "source", "batches": batches}
-    for name, aug in (("plain", False), ("augment", True)):
+    for name, aug in (("plain", False), ("augment", True), ("augment + intensity", {"intensity": True})):
         src = make_sample_source(dict(cfg, augment=aug), NET, 0, 0)
         next(src)
         torch.cuda.synchronize()
@@ -97,7 +121,8 @@ def train_part(cfg, batches):
     settings = training_settings(NET)
     trainer = Trainer(model, settings["in_shape"], lr=settings["lr"])
     res = {"part": "train", "steps": batches, "runs": []}
-    for name, aug in (("plain", False), ("augment", True), ("plain", False), ("augment", True)):   # alternating: the spread shows
+    three = (("plain", False), ("augment", True), ("augment + intensity", {"intensity": True}))
+    for name, aug in three + three:   # alternating: the spread shows
         src = PrefetchSource(make_sample_source(dict(cfg, augment=aug), NET, 0, 0), 4, 0)
         try:
             for _ in range(3):

@@ -1,5 +1,5 @@
 // Training targets of the 2-D setups (reference models/2d_mtlsd/train.py:29-164, 2d_lsd, 2d_affs) for a batch of sections
-// (their affinities: bsmi_train_affinity_targets_roi in train.hip, beside the erosion it shares with the 3-D entry).
+// (their affinities: bsmi_train_affinity_targets_roi in train_targets.hip, beside the erosion it shares with the 3-D entry).
 //
 //   lsd2d_targets_kernel   Add2DLSDs (gp/add_2d_lsds.py: lsd's LsdExtractor with sigma (0, s, s), 6 channels) of S sections in
 //                          one launch.  Voxels that share a sub-grid cell and a label share their statistics, so a thread owns a

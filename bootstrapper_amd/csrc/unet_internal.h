@@ -1,5 +1,5 @@
-// Internal structures of the U-Net engine shared by unet_api.hip (planner, forward) and train.hip (backward,
-// optimizer).  Not part of the C ABI.
+// Internal structures of the U-Net engine shared by unet_api.hip (planner, forward) and the training engine (train*.hip: backward,
+// optimizer; its own structures are in train_internal.h).  Not part of the C ABI.
 #pragma once
 #include <map>
 #include <memory>
@@ -148,13 +148,13 @@ struct PlanStep {
   // dense bf16 peak.  Exact for the implicit-GEMM and Winograd launches; the halo / box / first-pass kernels count their
   // algorithmic products (x 3 in the split mode), i.e. without their padding
   double exec_flops = 0;
-  // what the backward pass (train.hip) needs to know about a CONV step
+  // what the backward pass (train_plan.hip, train_wgrad.hip) needs to know about a CONV step
   struct PassSite* site = nullptr;
   int ci = 0;                        // stage index inside the ConvPass
   TDesc slots[kMaxConvTensors];      // source tensors of the launch
   int so[kMaxConvTensors][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};  // their origins (voxels)
   int nsl = 0;
-  // training (train.hip): this launch as a fused split-bf16 one over split copies of its f32 sources; used only while
+  // training (train_plan.hip): this launch as a fused split-bf16 one over split copies of its f32 sources; used only while
   // bsmi_unet::train_forward is set, so the f32 inference mode of the same plan stays exact f32
   struct TrainFwdX3* tx3 = nullptr;
 };
@@ -209,7 +209,7 @@ struct bsmi_unet {
   float* sk_ws = nullptr;  // split-K tail partial tiles + work-queue counters (conv_igemm.h)
   int sk_grid = 0;         // 0: not set up yet, -1: disabled
   int sk_request = -1;     // bsmi_unet_set_persistent_grid: -1 = CU count of the device, 0 = off
-  bsmi::TrainState* train = nullptr;  // train.hip
+  bsmi::TrainState* train = nullptr;  // train_internal.h
   bool train_forward = false;         // the forward pass of a training step is running (PlanStep::tx3)
   int train_split = 1;                // bsmi_unet_train_set_arithmetic
   int train_det = 0;                  // bsmi_unet_train_set_deterministic: ordered reductions instead of float atomics
@@ -221,6 +221,6 @@ namespace bsmi {
 // the cached launch plan of (precision, input shape); built on first use
 int get_plan(bsmi_unet* h, int precision, const int64_t in_shape[3], Plan** out);
 void free_train_state(bsmi_unet* h);
-int train_forward_conv_x3(bsmi_unet* h, const PlanStep& st, hipStream_t s);  // train.hip
-int train_refresh_f32_images(bsmi_unet* h, hipStream_t s);  // train.hip: f32 weight images left stale by the last optimizer step
+int train_forward_conv_x3(bsmi_unet* h, const PlanStep& st, hipStream_t s);  // train_plan.hip
+int train_refresh_f32_images(bsmi_unet* h, hipStream_t s);  // train_pack.hip: f32 weight images left stale by the last optimizer step
 }  // namespace bsmi

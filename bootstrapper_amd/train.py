@@ -17,7 +17,7 @@ as before.  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
 of each section in one launch each (csrc/train2d.hip).  `SyntheticSource` feeds the second-stage setups
 (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
-`synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train.hip).
+`synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
 """
 import ctypes as C
 import glob

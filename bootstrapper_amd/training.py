@@ -6,7 +6,7 @@ Reference being mirrored (paths relative to /root/reference/bootstrapper):
   models/3d_mtlsd/train.py          the same with (lsds, affs) heads; the loss is the sum of both
   training.py:96-137                fit(): implicit DDP -- one process per GPU, gradients averaged over the ranks
 
-The arithmetic (forward, loss, backward, Adam) is in libbsmi (csrc/train.hip); this module only wires buffers and,
+The arithmetic (forward, loss, backward, Adam) is in libbsmi (csrc/train*.hip); this module only wires buffers and,
 when torch.distributed is initialised, all-reduces the flat gradient buffer over RCCL (`nccl` backend) or gloo.
 """
 import ctypes as C

@@ -6,7 +6,7 @@ THEM; tests/test_backward_cpu.py chains the same operations over a small net aga
 emulations (and faulty emulations) of the kernels' arithmetic in the kernel's place.  This module holds what both share.
 It builds on tests/layer_ref.py (walk, Stage, split_bf16, compare, norm_err, MARGIN, G_OUT).
 
-Tensors are channels-last (D, H, W, C) arrays; weights are OIDHW.  The operations of csrc/train.hip:
+Tensors are channels-last (D, H, W, C) arrays; weights are OIDHW.  The operations of csrc/train_bwd.hip, train_wgrad.hip and train_plan.hip:
 
   masked gradient   g = dY [Y > 0] in the interior of a zero tensor with border P (border_of)
   weight gradient   dW[n, c, tap] = sum over output voxels m of g[m, n] x[m + tap, c], per source slot (columns cbase ..) and

@@ -1,4 +1,4 @@
-"""Per-launch parity of the training backward pass (csrc/train.hip): after ONE Trainer.forward_backward per case and arithmetic
+"""Per-launch parity of the training backward pass (csrc/train.hip and the train_*.hip files it walks): after ONE Trainer.forward_backward per case and arithmetic
 the plan is walked in reverse and every step's result is compared with a float64 computation of that one operation on the
 tensors AS THE DEVICE HOLDS THEM (tests/bwd_ref.py): forward activations from Model.debug_activation, gradients from
 Trainer.debug_tensor, parameters and their gradients from Trainer.read, what ran from Trainer.backward_steps.  Needs an MI355X.

@@ -23,7 +23,8 @@ def table():
 def test_code_objects_are_read(table):
     names = [k["name"] for k in table]
     assert len(table) > 500
-    for needle in ("head_kernel", "conv_igemm_kernel", "wino4_in_kernel", "blosc_plane_kernel", "wino_pack_kernel"):
+    for needle in ("head_kernel", "conv_igemm_kernel", "wino4_in_kernel", "blosc_plane_kernel", "wino_pack_kernel", "wgrad_x3_kernel",
+                   "lsd_targets_kernel"):
         assert any(needle in n for n in names), needle
 
 

@@ -1,4 +1,4 @@
-"""The device training step (csrc/train.hip through the C ABI) against the goldens the reference model, loss and
+"""The device training step (csrc/train*.hip through the C ABI) against the goldens the reference model, loss and
 optimizer produced (tests/golden/train_*.npz): loss, every parameter gradient, parameters after two Adam steps."""
 import json
 import os

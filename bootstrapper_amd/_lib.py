@@ -88,6 +88,12 @@ class BatchGraphArgs(C.Structure):
                 ("pair_counts_dev", C.c_void_p), ("counts_dev", C.c_void_p), ("edge_capacity", C.c_uint64)]
 
 
+class Aug2dDraw(C.Structure):
+    """bsmi_aug2d_draw of include/bsmi.h (64 bytes)"""
+    _fields_ = [("a", C.c_float * 4), ("src", C.c_float * 2), ("inv_spacing", C.c_float * 2), ("flags", C.c_int32), ("n", C.c_int32 * 2),
+                ("lattice_offset", C.c_int32), ("crop", C.c_int32 * 2), ("crop_offset", C.c_int32), ("reserved", C.c_int32)]
+
+
 CODEC_RAW, CODEC_ZLIB, CODEC_GZIP, CODEC_ZSTD, CODEC_LZ4, CODEC_BLOSC = range(6)
 BLOSC_LZ4, BLOSC_ZLIB, BLOSC_ZSTD = 1, 3, 4
 CHUNK_MISSING = 1
@@ -233,6 +239,10 @@ def _load():
         "bsmi_aug_impulse_f32": (i32, [i32, i64p, vp, C.c_uint64, C.c_uint64, vp]),
         "bsmi_aug_smooth_f32": (i32, [i32, i64p, vp, vp, C.POINTER(C.c_float), i32, vp]),
         "bsmi_aug_defect_f32": (i32, [i32, i64p, vp, vp, vp, C.c_float, i32, vp]),
+        "bsmi_aug2d_coords": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, i64p, i64p, i64p, vp, vp, C.c_int64, vp, vp]),
+        "bsmi_aug2d_sample_f32_u8": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
+        "bsmi_aug2d_sample_nearest_i64": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
+        "bsmi_aug2d_sample_nearest_u8": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

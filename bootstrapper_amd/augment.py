@@ -32,8 +32,8 @@ was written, so parity is in distribution.  x is raw in [0, 1], sections are the
 Declared quirk: the reference's ImpulseNoiseAugment draws its locations with the node's p, not with the pixel_p its call
 site passes (gp/impulse_noise_augment.py:58), so the default of `impulse_pixel_p` is q = impulse_p, what the reference
 executes; setting the key gives the documented 0.05 or any other value.
-NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, the 2-D setups,
-SyntheticSource, 3-D rotations.
+NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, SyntheticSource,
+3-D rotations.  The 2-D setups have their own geometric chain (augment2d.py, the key `augment2d`) and no intensity chain yet.
 """
 import ctypes as C
 import dataclasses
@@ -43,7 +43,8 @@ import numpy as np
 
 # what the trainer's log line names as missing: without `intensity`, and with it
 NOT_BUILT = "NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw"
-NOT_BUILT_WITH_INTENSITY = "DefectAugment's deformation and artifacts; augmentation of the 2-D setups and of synthetic labels"
+NOT_BUILT_WITH_INTENSITY = ("DefectAugment's deformation and artifacts; the intensity chain of the 2-D setups (their geometric chain is the key "
+                            "`augment2d`); augmentation of synthetic labels")
 MAX_LATTICE_NODES = 4096   # csrc/augment.hip: 48 KiB of offsets in LDS
 MAX_RADIUS = 6             # csrc/augment_intensity.hip: taps of the smoothing kernel, int(4 sigma + 0.5)
 STAT_PARTS = 16            # include/bsmi.h: BSMI_AUG_STAT_PARTS

@@ -15,7 +15,9 @@ intensity nodes of models/3d_affs/train.py:105-120 on raw (noise / intensity / g
 per node, csrc/augment_intensity.hip; specified rules, section 7k); without the key the batches are un-augmented crops,
 as before.  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
-of each section in one launch each (csrc/train2d.hip).  `SyntheticSource` feeds the second-stage setups
+of each section in one launch each (csrc/train2d.hip); with the train config key `augment2d` the geometric chain of
+models/2d_mtlsd/train.py:112-122 runs on the whole batch first, one coordinate launch and one resampling launch per array
+for the ten draws (augment2d.py, csrc/augment2d.hip; specified rules, section 7l).  `SyntheticSource` feeds the second-stage setups
 (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
 `synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
 """
@@ -187,11 +189,23 @@ class SectionSource:
     Batch: raw (in_channels * adj_slices, S, H, W) normalised to [-1, 1]; gt_lsds / lsds_weights (6, S, h, w);
     gt_affs / affs_weights (K, S, h, w)."""
 
-    def __init__(self, samples, input_shape, output_shape, adj_slices=1, device=0, seed=42, batch_size=10, lsds=None, affs=None):
+    def __init__(self, samples, input_shape, output_shape, adj_slices=1, device=0, seed=42, batch_size=10, lsds=None, affs=None,
+                 augment=None):
         """lsds: {"sigma", "downsample"} of net_config outputs.2d_lsds, or None; affs: {"neighborhood" (2-D offsets),
-        "grow_boundary"} of outputs.2d_affs, or None."""
+        "grow_boundary"} of outputs.2d_affs, or None.  augment: an augment2d.Aug2DParams (or True for the reference's
+        arguments) turns on the geometric chain SimpleAugment -> DeformAugment -> ShiftAugment of every draw (augment2d.py);
+        None: un-augmented windows, the same batches as without the argument."""
         if lsds is None and affs is None:
             raise ValueError("a 2-D setup has a 2d_lsds and / or a 2d_affs output")
+        self.augment = None
+        if augment is not None and augment is not False:
+            from . import augment2d as aug
+            self.augment = aug.Aug2DParams() if augment is True else augment
+            # refusals before any dataset is opened: a swap of non-square sections, a window that is not centred
+            if self.augment.simple:
+                aug.check_square(tuple(input_shape), tuple(output_shape))
+            if any((int(i) - int(o)) % 2 for i, o in zip(input_shape, output_shape)):
+                raise ValueError(f"augment2d: input_shape {list(input_shape)} - output_shape {list(output_shape)} must be even on every axis")
         self.samples = [(open_ds(s["raw"]), open_ds(s["labels"]), open_ds(s["mask"]) if s.get("mask") else None) for s in samples]
         self.inp, self.out = tuple(int(v) for v in input_shape), tuple(int(v) for v in output_shape)
         self.adj = int(adj_slices)
@@ -225,6 +239,13 @@ class SectionSource:
         self.lo = [max(a, b) for a, b in zip(self.lsd_ctx, lo)]
         self.hi = [max(a, b) for a, b in zip(self.lsd_ctx, hi)]
         self.tables = [None] * len(self.samples)
+        if self.augment is not None:
+            from . import augment2d as aug
+            # ... and before any read of data: a rotation on an anisotropic section grid (the voxel size is the stores' metadata)
+            if self.augment.deform_p > 0 and self.augment.rotate:
+                aug.check_rotation(self.vs)
+            # the map is evaluated over the union of the input section and the labels window: the labels may reach beyond the input
+            self.frame = aug.frame_of(self.inp, self.out, self.lo, self.hi)
 
     def _known(self, i, start, shape):
         """known-voxel mask (uint8) of the labels voxels [start, start + shape) of sample i, zeros beyond the volume"""
@@ -276,7 +297,70 @@ class SectionSource:
             if cnt >= need:
                 return i, z, y, x
 
+    def _next_augmented(self):
+        """One batch through the geometric chain.  Round 1 draws (location, plan) for the S slots in slot order -- the location
+        by _draw(), then augment2d.draw_plan2d's order --, reads one box per draw (augment2d.source_box2d of the plan over the
+        frame, zeros beyond the store) of raw (K sections), labels and mask, packs the S boxes, which differ in shape, into one
+        staging buffer per array and uploads each once, then runs the four launches: coordinates, labels, mask, raw.  The 5 %
+        test sees the augmented output window: one read-back of S counts after the mask launch decides which slots pass; the
+        failing slots are drawn again in slot order, location and plan, and only they are run again."""
+        from . import augment2d as aug
+        S, K = self.batch_size, self.adj
+        h, w = self.out
+        H, W = self.inp
+        lo, hi = self.lo, self.hi
+        need = -(-5 * h * w // 100)
+        window = ([c - l for c, l in zip(self.ctx, lo)], [h + lo[0] + hi[0], w + lo[1] + hi[1]])   # the labels window, in the input section's pixels
+        raw_t = torch.empty((K, S, H, W), dtype=torch.float32, device=self.dev)
+        lab_t = torch.empty((S, window[1][0], window[1][1]), dtype=torch.int64, device=self.dev)
+        unl_t = torch.empty(lab_t.shape, dtype=torch.uint8, device=self.dev)
+        slots = list(range(S))
+        for _ in range(1000):
+            plans, boxes, raws, labs, unls = [], [], [], [], []
+            for _s in slots:
+                i, z, y, x = self._draw()
+                plan = aug.draw_plan2d(self.rng, self.augment, self.inp, self.frame, K, self.vs)
+                box = aug.source_box2d(plan)
+                raw_ds, lab_ds, _ = self.samples[i]
+                vs, off = lab_ds.voxel_size, lab_ds.offset
+                size = (box[1][0] - box[0][0], box[1][1] - box[0][1])
+                # the box's origin in voxels of the labels volume: the input section starts ctx before the output window
+                start = (z, y - self.ctx[0] + box[0][0], x - self.ctx[1] + box[0][1])
+                world = [off[0] + (z - K // 2) * vs[0], off[1] + start[1] * vs[1], off[2] + start[2] * vs[2]]
+                raws.append(_read_world(raw_ds, world, (K,) + size, np.uint8))
+                world = [o + a * v for o, a, v in zip(off, start, vs)]
+                lab = _read_world(lab_ds, world, (1,) + size, lab_ds.dtype)[0]
+                # uint64 ids reinterpreted, not converted: the same bits as astype(int64)
+                labs.append(lab.view(np.int64) if lab.dtype == np.uint64 else lab.astype(np.int64, copy=False))
+                unls.append(self._known(i, start, (1,) + size)[0])
+                plans.append(plan)
+                boxes.append(box)
+            packed = aug.Packed2D(plans, boxes)
+            coords = aug.coords2d(packed, self.dev)
+            lab_r = aug.sample_labels2d(packed, coords, torch.from_numpy(packed.pack(labs, np.int64)).to(self.dev), window)
+            unl_r = aug.sample_mask2d(packed, coords, torch.from_numpy(packed.pack(unls, np.uint8)).to(self.dev), window)
+            # gp.Reject(mask=unlabelled, min_masked=0.05) on the augmented output window of every slot: the one read-back of the round
+            counts = unl_r[:, lo[0]:lo[0] + h, lo[1]:lo[1] + w].sum(dim=(1, 2), dtype=torch.int64)
+            raw_r = aug.sample_raw2d(packed, coords, torch.from_numpy(packed.pack(raws, np.uint8)).to(self.dev), ((0, 0), (H, W)))
+            ok = (counts >= need).cpu().numpy()
+            if ok.all() and len(slots) == S:
+                raw_t, lab_t, unl_t = raw_r, lab_r, unl_r
+            else:
+                keep = torch.from_numpy(np.nonzero(ok)[0]).to(self.dev)
+                dst = torch.tensor([slots[j] for j in np.nonzero(ok)[0]], dtype=torch.int64, device=self.dev)
+                raw_t.index_copy_(1, dst, raw_r.index_select(1, keep))
+                lab_t.index_copy_(0, dst, lab_r.index_select(0, keep))
+                unl_t.index_copy_(0, dst, unl_r.index_select(0, keep))
+            slots = [s for s, good in zip(slots, ok) if not good]
+            if not slots:
+                batch = {"raw": raw_t}
+                batch.update(self._targets(lab_t, unl_t))
+                return batch
+        raise RuntimeError("no training location with at least 5 % labelled voxels found after augmentation")
+
     def __next__(self):
+        if self.augment is not None:
+            return self._next_augmented()
         draws = [self._draw() for _ in range(self.batch_size)]
         h, w = self.out
         H, W = self.inp
@@ -298,6 +382,14 @@ class SectionSource:
         batch = {"raw": torch.from_numpy(raw).to(self.dev).float() * (1.0 / 255.0) * 2.0 - 1.0}
         lab_t = torch.from_numpy(lab).to(self.dev)
         unl_t = torch.from_numpy(unl).to(self.dev)
+        batch.update(self._targets(lab_t, unl_t))
+        return batch
+
+    def _targets(self, lab_t, unl_t):
+        """the targets of a batch from its labels and known-voxel mask over the labels window (S, h + lo + hi, w + lo + hi)"""
+        h, w = self.out
+        lo = self.lo
+        batch = {}
         if self.lsds is not None:
             c = self.lsd_ctx
             ys, xs = slice(lo[0] - c[0], lo[0] + h + c[0]), slice(lo[1] - c[1], lo[1] + w + c[1])
@@ -663,7 +755,12 @@ def make_sample_source(config, net_config, device=0, rank=0):
                                       "it covers 3d_affs, 3d_lsd and 3d_mtlsd")
         if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
             raise NotImplementedError(f"augment: not built for the 2-D setups (SectionSource, {setup_name(net_config)}); "
-                                      "it covers 3d_affs, 3d_lsd and 3d_mtlsd")
+                                      "it covers 3d_affs, 3d_lsd and 3d_mtlsd (the 2-D setups have the key `augment2d`)")
+    from .augment2d import Aug2DParams
+    augment2d = Aug2DParams.from_config(config.get("augment2d"))
+    if augment2d is not None and (set(net_config.get("inputs", {"raw": None})) != {"raw"} or not outs or set(outs) - {"2d_affs", "2d_lsds"}):
+        raise NotImplementedError(f"augment2d: not built for the {setup_name(net_config)} setup; it covers 2d_affs, 2d_lsd and 2d_mtlsd "
+                                  "(the first-stage 3-D setups have the key `augment`)")
     if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
         if not config.get("synthetic_labels", False):
             raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
@@ -673,7 +770,8 @@ def make_sample_source(config, net_config, device=0, rank=0):
     if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
         s = training_settings(net_config)
         return SectionSource(config["samples"], net_config["input_shape"], net_config["output_shape"], int(net_config.get("adj_slices", 1)),
-                             device=device, seed=42 + int(rank), batch_size=s["batch_size"], lsds=outs.get("2d_lsds"), affs=outs.get("2d_affs"))
+                             device=device, seed=42 + int(rank), batch_size=s["batch_size"], lsds=outs.get("2d_lsds"), affs=outs.get("2d_affs"),
+                             augment=augment2d)
     out3d, lsd3d = outs.get("3d_affs"), outs.get("3d_lsds")
     if set(outs) - {"3d_affs", "3d_lsds"} or not outs:
         raise NotImplementedError(f"the built-in sample source feeds the 2-D and 3-D setups, not the outputs {sorted(outs)}")
@@ -769,9 +867,13 @@ def run_training(config_file, device=0, batches=None, log=print):
             else:
                 log(f"note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`); not built: {NOT_BUILT} "
                     "(`intensity = true` inside the `[augment]` table turns them on)")
+        elif config.get("augment2d"):
+            from .augment2d import NOT_BUILT as NOT_BUILT_2D
+            log("note: geometric augmentation of the 2-D setups on the device (SimpleAugment, DeformAugment, ShiftAugment of every "
+                f"section of a batch: `augment2d`); not built: {NOT_BUILT_2D}")
         else:
             log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
-                "(`augment = true` turns on the geometric chain of the 3-D setups)")
+                "(`augment = true` turns on the geometric chain of the 3-D setups, `augment2d = true` that of the 2-D setups)")
         batches = make_sample_source(config, net_config, device, rank)
         if isinstance(batches, SyntheticSource):
             log(f"note: synthetic labels (synthetic_labels = true); not built: {SyntheticSource.NOT_BUILT}")

@@ -891,6 +891,65 @@ int bsmi_aug_smooth_f32(int device, const int64_t shape[3], float *x_dev, float 
 int bsmi_aug_defect_f32(int device, const int64_t shape[3], float *x_dev, const float *stats_dev, const int32_t *mode_dev,
                         float contrast_scale, int final_map, void *stream);
 
+/* ---- training augmentation of the 2-D setups: the geometric chain, a whole batch per launch (csrc/augment2d.hip; reference
+ * models/2d_mtlsd/train.py:112-122 and its 2d_affs / 2d_lsd siblings: SimpleAugment -> DeformAugment(spatial_dims=2) ->
+ * ShiftAugment under gp.Stack(10); the rules in full: DESIGN.md section 7l, tests/aug2d_ref.py) ----
+ * A step is S independent draws of one output section each, every draw with its own plan and its own crop, so the launches
+ * read one table of per-draw descriptors: ONE coordinate launch for all draws and all K adjacent sections of raw, ONE
+ * resampling launch per array for all draws.  Specified rules, like the 3-D chain: parity with gunpowder is in
+ * distribution.  Every random scalar is drawn by the caller.  Stateless, asynchronous on `stream`.
+ *
+ * With I = input_shape (H, W), c = (I - 1) / 2, F_lo = frame_offset (<= 0 per axis) and F = frame_shape (the frame
+ * [F_lo, F_lo + F) contains the input section [0, I): it is the union of the input section and the labels window, which may
+ * be the larger), aug2d_coords writes, for every draw s, section k and frame pixel (y, x) -- y, x in the input section's own
+ * pixels, possibly outside [0, I) -- the source coordinate in pixels of the draw's crop, all arithmetic in float32:
+ *   r = (y + shifts[s][0][k], x + shifts[s][1][k])         shifts_dev: int32 [S][2][K] or NULL (none)
+ *   d = r - c
+ *   t = (a0 * d_y + a1 * d_x, a2 * d_y + a3 * d_x) + E(r)   a = u * (cos, -sin, sin, cos)
+ *   E(r): bilinear interpolation of the draw's lattice, float32 [2][n_y][n_x] (component y, x in pixels) at lattice_offset
+ *         floats inside lattice_dev, or 0 when n = 0 x 0.  Per axis g = (r - F_lo) * inv_spacing + 1 (node j lies at F_lo +
+ *         (j - 1) * spacing), clamped to [0, n - 1]; cell = min(floor(g), n - 2), weight g - cell, a + w * (b - a) along x,
+ *         then y.  n_y * n_x <= 4096 (32 KiB of LDS per draw), else BSMI_ERR_INVALID.
+ *   if swap: t_y <-> t_x (needs H == W, else BSMI_ERR_INVALID)
+ *   s = src + (mirror bit set ? -t : t) per axis            src: the input section's centre in pixels of the crop
+ * coords_dev: float32 [S][K][2][F_h][F_w].  z is never interpolated: the z mirror only makes section k of raw read section
+ * K - 1 - k of the crop.
+ * aug2d_sample_* read the planes at the frame pixels [region_offset, region_offset + region_shape) (an offset inside the
+ * frame, not the input section) and gather from the draw's crop, every index clamped to that crop:
+ *   f32_u8:      crops_dev holds, per draw, K sections [K][crop_h][crop_w] at pixel K * crop_offset.  Bilinear in the plane
+ *                of section k_src through the coordinates of section k: cell floor(s), both corners clamped, a + w * (b - a)
+ *                along x, then y; out = (v * 2 - 255) / 255 into out_dev float32 [K][S][r_h][r_w], what the trainer reads.
+ *   nearest_i64, nearest_u8: one section per draw at pixel crop_offset; crop[clamp(floor(s + 0.5))] per axis, the sum and the
+ *                floor in float32, through the coordinates of section K / 2; out_dev [S][r_h][r_w].
+ * The table is passed twice: `draws` in host memory, which every call checks (S < 1, K < 1, more than 65535 (draw, section)
+ * pairs, a lattice of more than 4096 nodes or beyond lattice_floats, a swap of a non-square section, a crop beyond
+ * crop_pixels -- the pixels of crops_dev --, 2^31 coordinates / outputs or more: BSMI_ERR_INVALID), and `draws_dev`, the
+ * same bytes in device memory, which the kernels read.  Uploading the table is the caller's: once per batch for the four
+ * calls. */
+typedef struct bsmi_aug2d_draw {
+  float a[4];           /* A = u R(theta), row-major 2 x 2 */
+  float src[2];         /* c_src (y, x) */
+  float inv_spacing[2]; /* 1 / (node spacing in pixels), (y, x) */
+  int32_t flags;        /* bit 0 / 1 / 2: mirror z / y / x; bit 3: swap y <-> x, applied before the mirrors */
+  int32_t n[2];         /* lattice nodes (n_y, n_x); 0 x 0: no elastic term */
+  int32_t lattice_offset; /* of this draw's [2][n_y][n_x] floats in the packed lattice buffer */
+  int32_t crop[2];      /* the draw's crop: rows, columns */
+  int32_t crop_offset;  /* of the draw's crop in the packed crops, in pixels of one section */
+  int32_t reserved;     /* 0; the struct is 64 bytes */
+} bsmi_aug2d_draw;
+int bsmi_aug2d_coords(int device, const bsmi_aug2d_draw *draws, const bsmi_aug2d_draw *draws_dev, int S, int K, const int64_t input_shape[2],
+                      const int64_t frame_offset[2], const int64_t frame_shape[2], const int32_t *shifts_dev, const float *lattice_dev,
+                      int64_t lattice_floats, float *coords_dev, void *stream);
+int bsmi_aug2d_sample_f32_u8(int device, const bsmi_aug2d_draw *draws, const bsmi_aug2d_draw *draws_dev, int S, int K, const float *coords_dev,
+                             const int64_t frame_shape[2], const int64_t region_offset[2], const int64_t region_shape[2],
+                             const uint8_t *crops_dev, int64_t crop_pixels, float *out_dev, void *stream);
+int bsmi_aug2d_sample_nearest_i64(int device, const bsmi_aug2d_draw *draws, const bsmi_aug2d_draw *draws_dev, int S, int K,
+                                  const float *coords_dev, const int64_t frame_shape[2], const int64_t region_offset[2],
+                                  const int64_t region_shape[2], const int64_t *crops_dev, int64_t crop_pixels, int64_t *out_dev, void *stream);
+int bsmi_aug2d_sample_nearest_u8(int device, const bsmi_aug2d_draw *draws, const bsmi_aug2d_draw *draws_dev, int S, int K,
+                                 const float *coords_dev, const int64_t frame_shape[2], const int64_t region_offset[2],
+                                 const int64_t region_shape[2], const uint8_t *crops_dev, int64_t crop_pixels, uint8_t *out_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -94,6 +94,12 @@ class Aug2dDraw(C.Structure):
                 ("lattice_offset", C.c_int32), ("crop", C.c_int32 * 2), ("crop_offset", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Aug2dIDraw(C.Structure):
+    """bsmi_aug2d_idraw of include/bsmi.h (48 bytes)"""
+    _fields_ = [("seed", C.c_uint64), ("impulse_threshold", C.c_uint64), ("noise_sigma", C.c_float), ("contrast_scale", C.c_float),
+                ("nodes", C.c_int32), ("radius", C.c_int32), ("taps_offset", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 CODEC_RAW, CODEC_ZLIB, CODEC_GZIP, CODEC_ZSTD, CODEC_LZ4, CODEC_BLOSC = range(6)
 BLOSC_LZ4, BLOSC_ZLIB, BLOSC_ZSTD = 1, 3, 4
 CHUNK_MISSING = 1
@@ -243,6 +249,14 @@ def _load():
         "bsmi_aug2d_sample_f32_u8": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
         "bsmi_aug2d_sample_nearest_i64": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
         "bsmi_aug2d_sample_nearest_u8": (i32, [i32, C.POINTER(Aug2dDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp, C.c_int64, vp, vp]),
+        "bsmi_aug2d_sample_unit_f32_u8": (i32, [i32, C.POINTER(Aug2dDraw), vp, C.POINTER(Aug2dIDraw), vp, i32, i32, vp, i64p, i64p, i64p, vp,
+                                                C.c_int64, vp, vp]),
+        "bsmi_aug2d_noise_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp]),
+        "bsmi_aug2d_intensity_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, vp, vp, vp]),
+        "bsmi_aug2d_gamma_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, vp, vp]),
+        "bsmi_aug2d_impulse_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp]),
+        "bsmi_aug2d_smooth_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, vp, C.c_int64, vp]),
+        "bsmi_aug2d_defect_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, C.POINTER(C.c_int32), vp, i32, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),

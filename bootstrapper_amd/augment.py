@@ -33,7 +33,8 @@ Declared quirk: the reference's ImpulseNoiseAugment draws its locations with the
 site passes (gp/impulse_noise_augment.py:58), so the default of `impulse_pixel_p` is q = impulse_p, what the reference
 executes; setting the key gives the documented 0.05 or any other value.
 NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, SyntheticSource,
-3-D rotations.  The 2-D setups have their own geometric chain (augment2d.py, the key `augment2d`) and no intensity chain yet.
+3-D rotations.  The 2-D setups have their own chains, batched over the ten draws of a step (augment2d.py, the key `augment2d` and
+`intensity` inside it).
 """
 import ctypes as C
 import dataclasses
@@ -43,8 +44,8 @@ import numpy as np
 
 # what the trainer's log line names as missing: without `intensity`, and with it
 NOT_BUILT = "NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw"
-NOT_BUILT_WITH_INTENSITY = ("DefectAugment's deformation and artifacts; the intensity chain of the 2-D setups (their geometric chain is the key "
-                            "`augment2d`); augmentation of synthetic labels")
+NOT_BUILT_WITH_INTENSITY = ("DefectAugment's deformation and artifacts; augmentation of synthetic labels (the 2-D setups have their own key, "
+                            "`augment2d`)")
 MAX_LATTICE_NODES = 4096   # csrc/augment.hip: 48 KiB of offsets in LDS
 MAX_RADIUS = 6             # csrc/augment_intensity.hip: taps of the smoothing kernel, int(4 sigma + 0.5)
 STAT_PARTS = 16            # include/bsmi.h: BSMI_AUG_STAT_PARTS
@@ -72,36 +73,37 @@ class IntensityParams:
     contrast_scale: float = 0.1
 
     @classmethod
-    def from_config(cls, value):
-        """The key `intensity` of the `[augment]` table: absent / false -> None, true -> the defaults, a table -> overrides."""
+    def from_config(cls, value, key="augment.intensity"):
+        """The key `intensity` of the `[augment]` table: absent / false -> None, true -> the defaults, a table -> overrides.
+        key: how the errors name it (the 2-D setups parse the same table as `augment2d.intensity`)."""
         if value is None or value is False:
             return None
         if value is True:
             return cls()
         if not isinstance(value, dict):
-            raise ValueError(f"augment.intensity must be true, false or a table, not {value!r}")
+            raise ValueError(f"{key} must be true, false or a table, not {value!r}")
         names = [f.name for f in dataclasses.fields(cls)]
         unknown = sorted(set(value) - set(names))
         if unknown:
-            raise ValueError(f"unknown augment.intensity key(s) {', '.join(unknown)}; known: {', '.join(names)}")
+            raise ValueError(f"unknown {key} key(s) {', '.join(unknown)}; known: {', '.join(names)}")
         kw = {}
         for k, v in value.items():
             if k in ("scale", "shift", "gamma", "blur"):
                 kw[k] = tuple(float(x) for x in v)
                 if len(kw[k]) != 2 or not kw[k][0] <= kw[k][1] or (k != "shift" and kw[k][0] <= 0):
-                    raise ValueError(f"augment.intensity.{k} {v!r}: two numbers, low <= high" + ("" if k == "shift" else ", positive"))
+                    raise ValueError(f"{key}.{k} {v!r}: two numbers, low <= high" + ("" if k == "shift" else ", positive"))
                 if k == "blur" and int(4.0 * kw[k][1] + 0.5) > MAX_RADIUS:
-                    raise ValueError(f"augment.intensity.blur {v!r}: sigma below {(MAX_RADIUS + 0.5) / 4} (a radius int(4 sigma + 0.5) of at most {MAX_RADIUS})")
+                    raise ValueError(f"{key}.blur {v!r}: sigma below {(MAX_RADIUS + 0.5) / 4} (a radius int(4 sigma + 0.5) of at most {MAX_RADIUS})")
             else:
                 kw[k] = float(v)
                 if k in ("noise_var", "contrast_scale"):
                     if kw[k] < 0:
-                        raise ValueError(f"augment.intensity.{k} {v!r}: not negative")
+                        raise ValueError(f"{key}.{k} {v!r}: not negative")
                 elif kw[k] < 0 or kw[k] > 1:
-                    raise ValueError(f"augment.intensity.{k} {v!r}: a probability")
+                    raise ValueError(f"{key}.{k} {v!r}: a probability")
         p = cls(**kw)
         if p.prob_missing + p.prob_low_contrast > 1:
-            raise ValueError("augment.intensity: prob_missing + prob_low_contrast exceeds 1")
+            raise ValueError(f"{key}: prob_missing + prob_low_contrast exceeds 1")
         return p
 
 

@@ -23,7 +23,16 @@ the frame: node j at F_lo + (j - 1) spacing, j = 0 .. ceil((F_hi - F_lo - 1) / s
 Declared differences, as for the 3-D chain (augment.py): E is evaluated at every pixel (the reference's subsample=4 is a CPU
 shortcut); the 5 % rejection test sees the augmented output window, and it is per slot of the batch.  ShiftAugment's
 probability `shift_p` defaults to 1.0: the 2-D call sites pass no `p`, and 1.0 is gunpowder's documented default.
-NOT built: the intensity chain of the 2-D setups, augmentation of SyntheticSource.
+
+With `intensity` inside the table, raw then runs through the reference's intensity nodes (models/2d_mtlsd/train.py:123-136 and
+its siblings: NoiseAugment -> IntensityAugment -> GammaAugment -> ImpulseNoiseAugment -> SmoothAugment -> DefectAugment), again
+one launch per node for the WHOLE batch (csrc/augment2d_intensity.hip), driven by a table of per-draw descriptors and per-plane
+tables (PackedIntensity2D, apply_intensity2d).  The rule for a draw is augment.py's rule for the block (K, H, W) of its K
+sections, unchanged and the same device code, so the results are the same bits (DESIGN.md sections 7k and 7m): the Philox
+counter is the voxel's index inside the draw's own stack, smoothing runs over all three axes of the stack with the draw's
+sigma.  The call-site defaults that differ from the 3-D setups: prob_missing is 0.05 when adj_slices > 1 and 0 when it is 1
+(models/2d_mtlsd/train.py:136), resolved where adj_slices is known (Aug2DParams.intensity_for).
+NOT built: the deformation and artifact sources of DefectAugment, ClaheAugment, augmentation of SyntheticSource.
 """
 import ctypes as C
 import dataclasses
@@ -31,10 +40,11 @@ import math
 
 import numpy as np
 
-from .augment import _interval_mul
+from .augment import IntensityParams, _interval_mul
 
-NOT_BUILT = ("NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw for the 2-D "
-             "setups")
+# what the trainer's log line names as missing
+NOT_BUILT = "the deformation and artifact sources of DefectAugment, and ClaheAugment"
+INTENSITY_NODES = "NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw"
 MAX_LATTICE_NODES = 4096   # csrc/augment2d.hip: 32 KiB of offsets in LDS per draw
 
 
@@ -42,7 +52,10 @@ MAX_LATTICE_NODES = 4096   # csrc/augment2d.hip: 32 KiB of offsets in LDS per dr
 class Aug2DParams:
     """The arguments of the three nodes; the defaults are the reference's (models/2d_mtlsd/train.py:112-122).
     control_point_spacing / jitter_sigma: two world-unit values (y, x), None = the reference's (vs_y vs_z, vs_x vs_z) and
-    (2 vs_y, 2 vs_x).  shift_p: 1.0, gunpowder's documented default (the 2-D call passes none)."""
+    (2 vs_y, 2 vs_x).  shift_p: 1.0, gunpowder's documented default (the 2-D call passes none).  intensity: an
+    augment.IntensityParams turns on the intensity chain of raw; None (the default, also of `augment2d = true`): the geometric
+    chain alone.  Its prob_missing is None where the config gives none: the reference's default depends on adj_slices, so
+    intensity_for(K) resolves it."""
     simple: bool = True
     deform_p: float = 0.5
     scale_interval: tuple = (0.9, 1.1)
@@ -53,6 +66,14 @@ class Aug2DParams:
     prob_slip: float = 0.2
     prob_shift: float = 0.2
     shift_sigma: float = 3.0
+    intensity: IntensityParams = None
+
+    def intensity_for(self, sections):
+        """the IntensityParams of a setup with K = `sections`: prob_missing, where the config gives none, is the reference's 0.05
+        for K > 1 and 0 for K = 1 (models/2d_mtlsd/train.py:136); None without the key"""
+        if self.intensity is None or self.intensity.prob_missing is not None:
+            return self.intensity
+        return dataclasses.replace(self.intensity, prob_missing=0.05 if int(sections) > 1 else 0.0)
 
     @classmethod
     def from_config(cls, value):
@@ -69,7 +90,15 @@ class Aug2DParams:
             raise ValueError(f"unknown augment2d key(s) {', '.join(unknown)}; known: {', '.join(names)}")
         kw = {}
         for k, v in value.items():
-            if k in ("simple", "rotate"):
+            if k == "intensity":
+                # augment.IntensityParams' keys, checks and error texts.  Without prob_missing the table is checked with 0.05, the
+                # larger of the two defaults, and the field is left open for intensity_for
+                if v is True or (isinstance(v, dict) and "prob_missing" not in v):
+                    checked = IntensityParams.from_config(dict({} if v is True else v, prob_missing=0.05), "augment2d.intensity")
+                    kw[k] = dataclasses.replace(checked, prob_missing=None)
+                else:
+                    kw[k] = IntensityParams.from_config(v, "augment2d.intensity")
+            elif k in ("simple", "rotate"):
                 kw[k] = bool(v)
             elif k == "scale_interval":
                 kw[k] = tuple(float(x) for x in v)
@@ -321,7 +350,7 @@ def coords2d(packed, device=0):
     return out
 
 
-def _sample(fn, packed, coords_dev, crops, region, crop_dtype, out_dtype, sections):
+def _sample(fn, packed, coords_dev, crops, region, crop_dtype, out_dtype, sections, ipacked=None):
     import torch
     from . import _lib
     want = (packed.S, packed.K, 2) + packed.frame_shape
@@ -337,8 +366,9 @@ def _sample(fn, packed, coords_dev, crops, region, crop_dtype, out_dtype, sectio
     off, shape = (lo, packed.frame_shape) if region is None else (tuple(int(v) for v in region[0]), tuple(int(v) for v in region[1]))
     lead = (packed.K, packed.S) if crop_dtype == torch.uint8 and out_dtype == torch.float32 else (packed.S,)   # raw: the trainer's layout
     out = torch.empty(lead + shape, dtype=out_dtype, device=crops.device)
+    itable = () if ipacked is None else (ipacked.idraws, C.c_void_p(ipacked.upload(crops.device)[0].data_ptr()))
     _lib.check(getattr(_lib.lib, fn)(
-        crops.device.index, packed.draws, C.c_void_p(packed.dev[0].data_ptr()), packed.S, packed.K, C.c_void_p(coords_dev.data_ptr()),
+        crops.device.index, packed.draws, C.c_void_p(packed.dev[0].data_ptr()), *itable, packed.S, packed.K, C.c_void_p(coords_dev.data_ptr()),
         _i64x2(packed.frame_shape), _i64x2([o - l for o, l in zip(off, lo)]), _i64x2(shape), C.c_void_p(crops.data_ptr()), int(crops.numel()),
         C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(crops.device).cuda_stream)))
     return out
@@ -362,3 +392,203 @@ def sample_mask2d(packed, coords_dev, crops, region=None):
     """packed uint8 crops (one section per draw) -> uint8 (S, h, w): nearest, as the labels"""
     import torch
     return _sample("bsmi_aug2d_sample_nearest_u8", packed, coords_dev, crops, region, torch.uint8, torch.uint8, 1)
+
+
+# ---- the intensity chain of the whole batch (include/bsmi.h, "training augmentation of the 2-D setups: the intensity chain") ----
+
+NOISE, INTENSITY, GAMMA, IMPULSE, SMOOTH, DEFECT, TOUCHED = 1, 2, 4, 8, 16, 32, 64   # BSMI_AUG2D_*: the bits of a descriptor's `nodes`
+
+
+def node_bits(plan):
+    """the descriptor bits of an augment.IntensityPlan; TOUCHED = plan.applied"""
+    bits = ((NOISE if plan.noise_sigma is not None else 0) | (INTENSITY if plan.scale is not None else 0) | (GAMMA if plan.gamma is not None else 0)
+            | (IMPULSE if plan.impulse_threshold is not None else 0) | (SMOOTH if plan.weights is not None else 0)
+            | (DEFECT if plan.defect is not None else 0))
+    return bits | (TOUCHED if plan.applied else 0)
+
+
+class PackedIntensity2D:
+    """The S intensity plans of one batch (augment.IntensityPlan, each for a stack (K, H, W); a draw that is not to be touched
+    holds a plan without an applied node) in the form the launches read: the table of per-draw descriptors (bsmi_aug2d_idraw of
+    include/bsmi.h: node bits, seed, noise sigma, impulse threshold, contrast scale, smoothing radius and the offset of its taps),
+    the per-plane tables -- plane p = k * S + s of the trainer's layout [K][S][H][W] -- as ONE array `planes` [4][K * S] of 32-bit
+    words (rows: scale, shift, gamma exponent as float32; defect mode as int32; rows of draws without the node hold 1, 0, 1, 0)
+    and the taps of all smoothed draws packed into one float32 buffer.  Host memory; upload() makes the device copies, at most
+    three small uploads."""
+
+    def __init__(self, plans):
+        from . import _lib
+        if not plans:
+            raise ValueError("at least one plan")
+        shape = tuple(int(v) for v in plans[0].shape)
+        if len(shape) != 3 or any(tuple(p.shape) != shape for p in plans):
+            raise ValueError("the plans of a batch share one stack shape (K, H, W)")
+        self.S, self.K, self.section = len(plans), shape[0], shape[1:]
+        S, K = self.S, self.K
+        self.idraws = (_lib.Aug2dIDraw * S)()
+        self.planes = np.zeros((4, K * S), dtype=np.int32)
+        fl = self.planes.view(np.float32)
+        fl[0], fl[2] = 1.0, 1.0
+        taps, off = [], 0
+        self.nodes = 0
+        for s, plan in enumerate(plans):
+            d = self.idraws[s]
+            d.nodes = node_bits(plan)
+            self.nodes |= d.nodes
+            d.seed = int(plan.seed)
+            d.noise_sigma = float(plan.noise_sigma) if plan.noise_sigma is not None else 0.0
+            d.impulse_threshold = int(plan.impulse_threshold) if plan.impulse_threshold is not None else 0
+            d.contrast_scale = float(plan.contrast_scale)
+            for row, values in ((0, plan.scale), (1, plan.shift), (2, plan.gamma)):
+                if values is not None:
+                    fl[row, s::S] = self._per_section(values, np.float32, K)
+            if plan.defect is not None:
+                self.planes[3, s::S] = self._per_section(plan.defect, np.int32, K)
+            if plan.weights is not None:
+                w = np.ascontiguousarray(plan.weights, dtype=np.float32)
+                if w.ndim != 1 or w.size % 2 != 1:
+                    raise ValueError("weights: 2 radius + 1 taps")
+                d.radius, d.taps_offset = w.size // 2, off
+                taps.append(w)
+                off += w.size
+        self.taps = np.concatenate(taps) if taps else None
+        self.low_contrast = bool(((self.planes[3] == 3)).any())
+        self.dev = None   # device copies: (idraws, planes, taps)
+
+    @staticmethod
+    def _per_section(values, dtype, K):
+        v = np.asarray(values)
+        if v.dtype != dtype or v.shape != (K,):
+            raise ValueError(f"one {np.dtype(dtype)} value per section ({K}), not {v.dtype} {v.shape}")
+        return v
+
+    @property
+    def touched(self):
+        """per draw, whether the chain changes it (its plan's `applied`)"""
+        return [bool(d.nodes & TOUCHED) for d in self.idraws]
+
+    def upload(self, device=0):
+        """the device copies, once: the descriptor table, the per-plane tables, the taps (only where a draw is smoothed)"""
+        import torch
+        dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
+        if self.dev is None or self.dev[0].device != dev:
+            stream = torch.cuda.current_stream(dev)
+            table = torch.from_numpy(np.frombuffer(self.idraws, dtype=np.uint8).copy()).to(dev)
+            planes = torch.from_numpy(self.planes).to(dev)
+            taps = torch.from_numpy(self.taps).to(dev) if self.taps is not None else None
+            self.dev = (table, planes, taps)
+            for t in self.dev:   # uploaded on this stream, read by the launches queued on it
+                if t is not None:
+                    t.record_stream(stream)
+        return self.dev
+
+
+def sample_unit2d(packed, coords_dev, crops, ipacked, region=None):
+    """sample_raw2d for a batch that goes on through the intensity chain: the draws `ipacked` (a PackedIntensity2D of the same S
+    draws) marks as touched are written v / 255, what the chain starts from; the others v * 2 / 255 - 1, bit-equal to sample_raw2d"""
+    import torch
+    if ipacked.S != packed.S or ipacked.K != packed.K:
+        raise ValueError(f"intensity table of {ipacked.S} draws x {ipacked.K} sections for a batch of {packed.S} x {packed.K}")
+    return _sample("bsmi_aug2d_sample_unit_f32_u8", packed, coords_dev, crops, region, torch.uint8, torch.float32, packed.K, ipacked)
+
+
+def _batch(x, ipacked):
+    """the leading arguments of a batched node: device, the table twice, S, K, the section's shape, the batch"""
+    import torch
+    want = (ipacked.K, ipacked.S) + tuple(ipacked.section)
+    if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_cuda or not x.is_contiguous():
+        raise ValueError(f"the batch must be a contiguous float32 CUDA tensor {want}")
+    table = ipacked.upload(x.device)[0]
+    return (x.device.index, ipacked.idraws, C.c_void_p(table.data_ptr()), ipacked.S, ipacked.K, _i64x2(ipacked.section), C.c_void_p(x.data_ptr()))
+
+
+def _stream(x):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+
+
+def _row(ipacked, x, row):
+    planes = ipacked.upload(x.device)[1]
+    return C.c_void_p(planes[row].data_ptr())
+
+
+def plane_stats(x):
+    """float32 CUDA (K * S, 3): mean, min and max of every plane of the batch (K, S, H, W), in augment.section_stats' fixed order"""
+    from .augment import section_stats
+    return section_stats(x.view((x.shape[0] * x.shape[1],) + tuple(x.shape[2:])))
+
+
+def _stats(x, stats):
+    import torch
+    if stats.dtype != torch.float32 or tuple(stats.shape) != (x.shape[0] * x.shape[1], 3) or stats.device != x.device or not stats.is_contiguous():
+        raise ValueError("stats must be plane_stats of the batch: float32 (K * S, 3) on its device")
+    return C.c_void_p(stats.data_ptr())
+
+
+def noise2d(x, ipacked):
+    """NoiseAugment of every draw that has it, one launch; x (K, S, H, W) in place"""
+    from . import _lib
+    _lib.check(_lib.lib.bsmi_aug2d_noise_f32(*_batch(x, ipacked), _stream(x)))
+    return x
+
+
+def impulse2d(x, ipacked):
+    from . import _lib
+    _lib.check(_lib.lib.bsmi_aug2d_impulse_f32(*_batch(x, ipacked), _stream(x)))
+    return x
+
+
+def intensity2d(x, ipacked, stats):
+    from . import _lib
+    _lib.check(_lib.lib.bsmi_aug2d_intensity_f32(*_batch(x, ipacked), _stats(x, stats), _row(ipacked, x, 0), _row(ipacked, x, 1), _stream(x)))
+    return x
+
+
+def gamma2d(x, ipacked, stats):
+    from . import _lib
+    _lib.check(_lib.lib.bsmi_aug2d_gamma_f32(*_batch(x, ipacked), _stats(x, stats), _row(ipacked, x, 2), _stream(x)))
+    return x
+
+
+def smooth2d(x, ipacked, tmp=None):
+    """SmoothAugment of every draw that has it, each with its own taps over its own K sections: two launches"""
+    import torch
+    from . import _lib
+    if ipacked.taps is None:
+        return x
+    tmp = torch.empty_like(x) if tmp is None else tmp
+    taps = ipacked.upload(x.device)[2]
+    _lib.check(_lib.lib.bsmi_aug2d_smooth_f32(*_batch(x, ipacked), C.c_void_p(tmp.data_ptr()), C.c_void_p(taps.data_ptr()), int(taps.numel()),
+                                              _stream(x)))
+    return x
+
+
+def defect2d(x, ipacked, stats=None, final_map=False):
+    """DefectAugment of every draw that has it (stats: plane_stats, needed where a section is low-contrast); final_map: then
+    2 x - 1 on every touched draw"""
+    from . import _lib
+    modes = ipacked.planes[3]
+    _lib.check(_lib.lib.bsmi_aug2d_defect_f32(*_batch(x, ipacked), _stats(x, stats) if stats is not None else None,
+                                              modes.ctypes.data_as(C.POINTER(C.c_int32)), _row(ipacked, x, 3), 1 if final_map else 0, _stream(x)))
+    return x
+
+
+def apply_intensity2d(raw_t, packed, final_map=True):
+    """The intensity chain of the whole batch raw_t (K, S, H, W) -- touched draws in [0, 1], as sample_unit2d writes them -- in
+    place: one launch per node that some draw applies (smooth: two), the plane statistics its successor needs, then 2 x - 1 on
+    the touched draws.  At most 13 launches whatever S is; a batch without a touched draw launches nothing.  Draw s comes out as
+    augment.apply_intensity leaves the stack raw_t[:, s] under its plan, bit for bit; an untouched draw stays bit-equal."""
+    n = packed.nodes
+    if not n & TOUCHED:
+        return raw_t
+    if n & NOISE:
+        noise2d(raw_t, packed)
+    if n & INTENSITY:
+        intensity2d(raw_t, packed, plane_stats(raw_t))
+    if n & GAMMA:
+        gamma2d(raw_t, packed, plane_stats(raw_t))
+    if n & IMPULSE:
+        impulse2d(raw_t, packed)
+    if n & SMOOTH:
+        smooth2d(raw_t, packed)
+    return defect2d(raw_t, packed, plane_stats(raw_t) if packed.low_contrast else None, final_map)

@@ -109,12 +109,16 @@ __global__ __launch_bounds__(256) void aug2d_sample_nearest_kernel(Aug2dRegion g
 }
 
 // bilinear on u8 in the plane of section k_src, written as (v * 2 - 255) / 255 into [K][S][rh][rw]; both cell corners clamped.
-// grid.y: (draw, section); the crop of a draw is K sections
+// grid.y: (draw, section); the crop of a draw is K sections.  kUnit: a draw whose intensity descriptor has BSMI_AUG2D_TOUCHED is
+// written v / 255 instead (Normalize alone), what the intensity chain of augment2d_intensity.hip starts from
+template <bool kUnit>
 __global__ __launch_bounds__(256) void aug2d_sample_f32_u8_kernel(Aug2dRegion g, const bsmi_aug2d_draw* __restrict__ draws,
-                                                                  const float* __restrict__ coords, const uint8_t* __restrict__ crops,
-                                                                  float* __restrict__ out) {
+                                                                  const bsmi_aug2d_idraw* __restrict__ idraws, const float* __restrict__ coords,
+                                                                  const uint8_t* __restrict__ crops, float* __restrict__ out) {
   const int s = (int)blockIdx.y / g.K, k = (int)blockIdx.y - s * g.K;
   const bsmi_aug2d_draw d = draws[s];
+  bool unit = false;
+  if constexpr (kUnit) unit = idraws[s].nodes & BSMI_AUG2D_TOUCHED;
   const int ch = d.crop[0], cw = d.crop[1];
   const int ks = (d.flags & 1) ? g.K - 1 - k : k;
   const uint32_t fp = (uint32_t)g.fh * g.fw, rp = (uint32_t)g.rh * g.rw;
@@ -135,7 +139,10 @@ __global__ __launch_bounds__(256) void aug2d_sample_f32_u8_kernel(Aug2dRegion g,
     const uint8_t* r0 = crop + (size_t)y0 * cw;
     const uint8_t* r1 = crop + (size_t)y1 * cw;
     const float v = lerp(lerp((float)r0[x0], (float)r0[x1], wx), lerp((float)r1[x0], (float)r1[x1], wx), wy);
-    o[idx] = (v * 2.0f - 255.0f) / 255.0f;  // on a pixel centre the numerator is exact: half an ulp of v * 2 / 255 - 1
+    if (kUnit && unit)
+      o[idx] = v / 255.0f;
+    else
+      o[idx] = (v * 2.0f - 255.0f) / 255.0f;  // on a pixel centre the numerator is exact: half an ulp of v * 2 / 255 - 1
   }
 }
 
@@ -259,8 +266,26 @@ int bsmi_aug2d_sample_f32_u8(int device, const bsmi_aug2d_draw* draws, const bsm
   Aug2dRegion g;
   if (int rc = make_region(draws, draws_dev, S, K, frame_shape, region_offset, region_shape, crop_pixels, K, K, &g)) return rc;
   BSMI_HIP(hipSetDevice(device));
-  hipLaunchKernelGGL(aug2d_sample_f32_u8_kernel, dim3(aug2d_grid((size_t)g.rh * g.rw), S * K), dim3(256), 0, (hipStream_t)stream, g, draws_dev,
-                     coords_dev, crops_dev, out_dev);
+  hipLaunchKernelGGL(aug2d_sample_f32_u8_kernel<false>, dim3(aug2d_grid((size_t)g.rh * g.rw), S * K), dim3(256), 0, (hipStream_t)stream, g, draws_dev,
+                     (const bsmi_aug2d_idraw*)nullptr, coords_dev, crops_dev, out_dev);
+  BSMI_HIP(hipGetLastError());
+  return BSMI_OK;
+}
+
+// the resampling of raw stays in this translation unit with its kernel; the rest of the intensity chain is augment2d_intensity.hip
+int bsmi_aug2d_sample_unit_f32_u8(int device, const bsmi_aug2d_draw* draws, const bsmi_aug2d_draw* draws_dev, const bsmi_aug2d_idraw* idraws,
+                                  const bsmi_aug2d_idraw* idraws_dev, int S, int K, const float* coords_dev, const int64_t frame_shape[2],
+                                  const int64_t region_offset[2], const int64_t region_shape[2], const uint8_t* crops_dev, int64_t crop_pixels,
+                                  float* out_dev, void* stream) {
+  if (!coords_dev || !crops_dev || !out_dev) BSMI_FAIL(BSMI_ERR_INVALID, "null argument");
+  Aug2dRegion g;
+  if (int rc = make_region(draws, draws_dev, S, K, frame_shape, region_offset, region_shape, crop_pixels, K, K, &g)) return rc;
+  if (!idraws || !idraws_dev) BSMI_FAIL(BSMI_ERR_INVALID, "null intensity descriptor table");
+  for (int s = 0; s < S; ++s)
+    if (idraws[s].nodes < 0 || idraws[s].nodes > 127) BSMI_FAIL(BSMI_ERR_INVALID, "draw %d: nodes %d: a mask of bits 0..6", s, idraws[s].nodes);
+  BSMI_HIP(hipSetDevice(device));
+  hipLaunchKernelGGL(aug2d_sample_f32_u8_kernel<true>, dim3(aug2d_grid((size_t)g.rh * g.rw), S * K), dim3(256), 0, (hipStream_t)stream, g, draws_dev,
+                     idraws_dev, coords_dev, crops_dev, out_dev);
   BSMI_HIP(hipGetLastError());
   return BSMI_OK;
 }

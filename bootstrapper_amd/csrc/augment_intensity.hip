@@ -6,32 +6,12 @@
 // All of it is memory-bound and small (1.2 M voxels at the 3d_mtlsd shape): lanes run along x, rows are read and written
 // whole.  Every random scalar is drawn by the caller; the per-voxel ones come from Philox4x32-10 keyed by the caller's seed.
 #include "common.h"
+#include "augment_intensity.h"
 
 namespace bsmi {
 namespace {
 
-constexpr int kStatParts = BSMI_AUG_STAT_PARTS;   // partial reductions per section
-constexpr int kMaxRadius = BSMI_AUG_MAX_RADIUS;   // of the smoothing kernel: int(4 sigma + 0.5) for sigma <= 1.5
-constexpr int kTileY = 16, kTileX = 64;           // output tile of the y/x smoothing pass
-
-// Philox4x32-10 (Salmon et al., SC'11) on the counter (c0, 0, 0, 0) with key (k0, k1)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t k0, uint32_t k1, uint32_t o[4]) {
-  uint32_t a = c0, b = 0, c = 0, d = 0;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, a), lo0 = 0xD2511F53u * a;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c), lo1 = 0xCD9E8D57u * c;
-    a = hi1 ^ b ^ k0;
-    b = lo1;
-    c = hi0 ^ d ^ k1;
-    d = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  o[0] = a, o[1] = b, o[2] = c, o[3] = d;
-}
-
-__device__ __forceinline__ float clip01(float v) { return fminf(fmaxf(v, 0.0f), 1.0f); }
+using namespace augi;
 
 struct Block {
   uint32_t total;   // D * H * W, fewer than 2^31
@@ -41,21 +21,15 @@ struct Block {
 // x = clip(x + sigma * n), n = sqrt(-2 ln u1) cos(2 pi u2) from words 0 and 1 of the voxel's Philox output
 __global__ __launch_bounds__(256) void aug_noise_kernel(Block g, float* __restrict__ x, uint32_t k0, uint32_t k1, float sigma) {
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < g.total; idx += gridDim.x * blockDim.x) {
-    uint32_t o[4];
-    philox4x32_10(idx, k0, k1, o);
-    const float u1 = (float)((o[0] >> 8) + 1u) * 0x1p-24f;   // (0, 1]: exact, at most 2^24
-    const float u2 = (float)(o[1] >> 8) * 0x1p-24f;          // [0, 1)
-    const float n = sqrtf(-2.0f * logf(u1)) * cospif(2.0f * u2);
-    x[idx] = clip01(x[idx] + sigma * n);
+    x[idx] = noise_value(x[idx], idx, k0, k1, sigma);
   }
 }
 
 // a voxel is replaced iff word 2 < threshold (threshold 2^32: always), by (word 3 >> 8) * 2^-24
 __global__ __launch_bounds__(256) void aug_impulse_kernel(Block g, float* __restrict__ x, uint32_t k0, uint32_t k1, uint64_t threshold) {
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < g.total; idx += gridDim.x * blockDim.x) {
-    uint32_t o[4];
-    philox4x32_10(idx, k0, k1, o);
-    if ((uint64_t)o[2] < threshold) x[idx] = (float)(o[3] >> 8) * 0x1p-24f;
+    float v;
+    if (impulse_value(idx, k0, k1, threshold, &v)) x[idx] = v;
   }
 }
 
@@ -108,8 +82,7 @@ __global__ __launch_bounds__(256) void aug_intensity_kernel(Block g, float* __re
                                                             const float* __restrict__ scale, const float* __restrict__ shift) {
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < g.total; idx += gridDim.x * blockDim.x) {
     const uint32_t z = idx / g.plane;
-    const float m = stats[3 * z];
-    x[idx] = clip01(m + (x[idx] - m) * scale[z] + shift[z]);
+    x[idx] = intensity_value(x[idx], stats[3 * z], scale[z], shift[z]);
   }
 }
 
@@ -122,9 +95,7 @@ __global__ __launch_bounds__(256) void aug_gamma_kernel(Block g, float* __restri
     const float a = stats[3 * z + 1], b = stats[3 * z + 2];
     const float range = b - a;
     if (!(range > 1e-3f)) continue;
-    const float t = (x[idx] - a) / range;
-    const float p = t > 0.0f ? powf(t, gamma[z]) : 0.0f;
-    x[idx] = fminf(fmaxf(p * range + a, a), b);
+    x[idx] = gamma_value(x[idx], a, b, range, gamma[z]);
   }
 }
 
@@ -133,15 +104,7 @@ __global__ __launch_bounds__(256) void aug_defect_kernel(Block g, float* __restr
                                                          const int32_t* __restrict__ mode, float contrast_scale, int final_map) {
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < g.total; idx += gridDim.x * blockDim.x) {
     const uint32_t z = idx / g.plane;
-    const int md = mode ? mode[z] : 0;
-    float v = x[idx];
-    if (md == 1) v = 0.0f;
-    else if (md == 2) v = 1.0f;
-    else if (md == 3) {
-      const float m = stats[3 * z];
-      v = m + (v - m) * contrast_scale;
-    }
-    x[idx] = final_map ? 2.0f * v - 1.0f : v;
+    x[idx] = defect_value(x[idx], mode ? mode[z] : 0, stats + 3 * z, contrast_scale, final_map);
   }
 }
 
@@ -150,53 +113,19 @@ struct Taps {
   float w[2 * kMaxRadius + 1];
 };
 
-// scipy's "reflect" (d c b a | a b c d), repeated as often as needed: period 2 n
-__device__ __forceinline__ int reflect(int i, int n) {
-  const int p = 2 * n;
-  i %= p;
-  if (i < 0) i += p;
-  return i < n ? i : p - 1 - i;
-}
-
 // the z pass: whole rows, one tap per section read
 __global__ __launch_bounds__(256) void aug_smooth_z_kernel(Block g, int D, Taps t, const float* __restrict__ in, float* __restrict__ out) {
   for (uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x; idx < g.total; idx += gridDim.x * blockDim.x) {
     const int z = (int)(idx / g.plane);
     const uint32_t p = idx - (uint32_t)z * g.plane;
-    float acc = 0.0f;
-    for (int k = 0; k <= 2 * t.radius; ++k) acc += t.w[k] * in[(size_t)reflect(z + k - t.radius, D) * g.plane + p];
-    out[idx] = acc;
+    out[idx] = tap_sum(t.radius, t.w, [&](int k) { return in[(size_t)reflect(z + k - t.radius, D) * g.plane + p]; });
   }
 }
 
 // the y and x passes from one tile staged with its halo in LDS: y into `mid` (halo columns included), x out of it
 __global__ __launch_bounds__(256) void aug_smooth_yx_kernel(int H, int W, Taps t, const float* __restrict__ in, float* __restrict__ out) {
-  constexpr int kCols = kTileX + 2 * kMaxRadius + 1;   // + 1: rows start on different banks
-  __shared__ float tile[kTileY + 2 * kMaxRadius][kCols];
-  __shared__ float mid[kTileY][kCols];
-  const int r = t.radius;
-  const int cols = kTileX + 2 * r, rows = kTileY + 2 * r;
-  const int x0 = blockIdx.x * kTileX, y0 = blockIdx.y * kTileY;
-  const float* sec = in + (size_t)blockIdx.z * H * W;
-  for (int i = threadIdx.x; i < rows * cols; i += 256) {
-    const int ly = i / cols, lx = i - ly * cols;
-    tile[ly][lx] = sec[(size_t)reflect(y0 + ly - r, H) * W + reflect(x0 + lx - r, W)];
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kTileY * cols; i += 256) {
-    const int ly = i / cols, lx = i - ly * cols;
-    float acc = 0.0f;
-    for (int k = 0; k <= 2 * r; ++k) acc += t.w[k] * tile[ly + k][lx];
-    mid[ly][lx] = acc;
-  }
-  __syncthreads();
-  const int tx = threadIdx.x % kTileX, x = x0 + tx;
-  if (x >= W) return;
-  for (int ly = threadIdx.x / kTileX; ly < kTileY && y0 + ly < H; ly += 256 / kTileX) {
-    float acc = 0.0f;
-    for (int k = 0; k <= 2 * r; ++k) acc += t.w[k] * mid[ly][tx + k];
-    out[((size_t)blockIdx.z * H + (y0 + ly)) * W + x] = acc;
-  }
+  const size_t sec = (size_t)blockIdx.z * H * W;
+  smooth_yx_tile(H, W, t.radius, t.w, in + sec, out + sec);
 }
 
 unsigned grid_of(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, 2048); }

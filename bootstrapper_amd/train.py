@@ -17,8 +17,9 @@ as before.  `SectionSource`
 does the same for the 2-D setups (models/2d_mtlsd/train.py:29-164): ten sections per batch, Add2DLSDs and the affinities
 of each section in one launch each (csrc/train2d.hip); with the train config key `augment2d` the geometric chain of
 models/2d_mtlsd/train.py:112-122 runs on the whole batch first, one coordinate launch and one resampling launch per array
-for the ten draws (augment2d.py, csrc/augment2d.hip; specified rules, section 7l).  `SyntheticSource` feeds the second-stage setups
-(models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
+for the ten draws (augment2d.py, csrc/augment2d.hip; specified rules, section 7l), and with `intensity` inside that table the
+intensity nodes of raw after it, one launch per node for the ten draws (csrc/augment2d_intensity.hip; section 7m).
+`SyntheticSource` feeds the second-stage setups (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
 `synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
 """
 import ctypes as C
@@ -193,8 +194,9 @@ class SectionSource:
                  augment=None):
         """lsds: {"sigma", "downsample"} of net_config outputs.2d_lsds, or None; affs: {"neighborhood" (2-D offsets),
         "grow_boundary"} of outputs.2d_affs, or None.  augment: an augment2d.Aug2DParams (or True for the reference's
-        arguments) turns on the geometric chain SimpleAugment -> DeformAugment -> ShiftAugment of every draw (augment2d.py);
-        None: un-augmented windows, the same batches as without the argument."""
+        arguments) turns on the geometric chain SimpleAugment -> DeformAugment -> ShiftAugment of every draw (augment2d.py),
+        and with its field `intensity` set the intensity chain of raw after it, batched over the draws; None: un-augmented
+        windows, the same batches as without the argument."""
         if lsds is None and affs is None:
             raise ValueError("a 2-D setup has a 2d_lsds and / or a 2d_affs output")
         self.augment = None
@@ -246,6 +248,8 @@ class SectionSource:
                 aug.check_rotation(self.vs)
             # the map is evaluated over the union of the input section and the labels window: the labels may reach beyond the input
             self.frame = aug.frame_of(self.inp, self.out, self.lo, self.hi)
+            # prob_missing, where the config gives none, depends on adj_slices (models/2d_mtlsd/train.py:136)
+            self.intensity = self.augment.intensity_for(self.adj)
 
     def _known(self, i, start, shape):
         """known-voxel mask (uint8) of the labels voxels [start, start + shape) of sample i, zeros beyond the volume"""
@@ -303,7 +307,11 @@ class SectionSource:
         frame, zeros beyond the store) of raw (K sections), labels and mask, packs the S boxes, which differ in shape, into one
         staging buffer per array and uploads each once, then runs the four launches: coordinates, labels, mask, raw.  The 5 %
         test sees the augmented output window: one read-back of S counts after the mask launch decides which slots pass; the
-        failing slots are drawn again in slot order, location and plan, and only they are run again."""
+        failing slots are drawn again in slot order, location and plan, and only they are run again.
+        With augment2d.intensity, a round draws, after that read-back, one intensity plan (augment.draw_intensity_plan's order, for
+        the stack (K, H, W)) for every slot it accepted, in slot order -- a rejected slot takes none of these draws --, its raw
+        launch then writes the draws whose plan applies a node as v / 255, and after the last round ONE chain of batched launches
+        (augment2d.apply_intensity2d) runs over the whole batch; a draw whose plan applies no node stays bit-equal."""
         from . import augment2d as aug
         S, K = self.batch_size, self.adj
         h, w = self.out
@@ -315,6 +323,7 @@ class SectionSource:
         lab_t = torch.empty((S, window[1][0], window[1][1]), dtype=torch.int64, device=self.dev)
         unl_t = torch.empty(lab_t.shape, dtype=torch.uint8, device=self.dev)
         slots = list(range(S))
+        iplans, ipacked = [None] * S, None   # with augment2d.intensity: the accepted plan of every slot; the table of a round that filled the batch
         for _ in range(1000):
             plans, boxes, raws, labs, unls = [], [], [], [], []
             for _s in slots:
@@ -341,8 +350,18 @@ class SectionSource:
             unl_r = aug.sample_mask2d(packed, coords, torch.from_numpy(packed.pack(unls, np.uint8)).to(self.dev), window)
             # gp.Reject(mask=unlabelled, min_masked=0.05) on the augmented output window of every slot: the one read-back of the round
             counts = unl_r[:, lo[0]:lo[0] + h, lo[1]:lo[1] + w].sum(dim=(1, 2), dtype=torch.int64)
-            raw_r = aug.sample_raw2d(packed, coords, torch.from_numpy(packed.pack(raws, np.uint8)).to(self.dev), ((0, 0), (H, W)))
+            if self.intensity is None:
+                raw_r = aug.sample_raw2d(packed, coords, torch.from_numpy(packed.pack(raws, np.uint8)).to(self.dev), ((0, 0), (H, W)))
             ok = (counts >= need).cpu().numpy()
+            if self.intensity is not None:
+                from .augment import IntensityPlan, draw_intensity_plan
+                # the intensity draws come after the test has accepted a slot: a rejected one takes none of them
+                drawn = [draw_intensity_plan(self.rng, self.intensity, (K, H, W)) if good else IntensityPlan((K, H, W)) for good in ok]
+                for s, good, ip in zip(slots, ok, drawn):
+                    if good:
+                        iplans[s] = ip
+                ipacked = aug.PackedIntensity2D(drawn)
+                raw_r = aug.sample_unit2d(packed, coords, torch.from_numpy(packed.pack(raws, np.uint8)).to(self.dev), ipacked, ((0, 0), (H, W)))
             if ok.all() and len(slots) == S:
                 raw_t, lab_t, unl_t = raw_r, lab_r, unl_r
             else:
@@ -353,6 +372,9 @@ class SectionSource:
                 unl_t.index_copy_(0, dst, unl_r.index_select(0, keep))
             slots = [s for s, good in zip(slots, ok) if not good]
             if not slots:
+                if self.intensity is not None:
+                    # the round's own table where one round filled the batch, else one of the plans the slots were accepted with
+                    aug.apply_intensity2d(raw_t, ipacked if ipacked.S == S else aug.PackedIntensity2D(iplans))
                 batch = {"raw": raw_t}
                 batch.update(self._targets(lab_t, unl_t))
                 return batch
@@ -868,9 +890,15 @@ def run_training(config_file, device=0, batches=None, log=print):
                 log(f"note: geometric augmentation on the device (SimpleAugment, DeformAugment, ShiftAugment: `augment`); not built: {NOT_BUILT} "
                     "(`intensity = true` inside the `[augment]` table turns them on)")
         elif config.get("augment2d"):
-            from .augment2d import NOT_BUILT as NOT_BUILT_2D
-            log("note: geometric augmentation of the 2-D setups on the device (SimpleAugment, DeformAugment, ShiftAugment of every "
-                f"section of a batch: `augment2d`); not built: {NOT_BUILT_2D}")
+            from .augment2d import INTENSITY_NODES, NOT_BUILT as NOT_BUILT_2D, Aug2DParams
+            if Aug2DParams.from_config(config["augment2d"]).intensity is not None:
+                log("note: geometric augmentation of the 2-D setups on the device (SimpleAugment, DeformAugment, ShiftAugment of every "
+                    f"section of a batch: `augment2d`) and the intensity chain of raw ({INTENSITY_NODES}: `augment2d.intensity`), "
+                    f"both batched over the draws of a step; not built: {NOT_BUILT_2D}")
+            else:
+                log("note: geometric augmentation of the 2-D setups on the device (SimpleAugment, DeformAugment, ShiftAugment of every "
+                    f"section of a batch: `augment2d`); off: {INTENSITY_NODES} (`intensity = true` inside the `[augment2d]` table turns "
+                    f"them on); not built: {NOT_BUILT_2D}")
         else:
             log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
                 "(`augment = true` turns on the geometric chain of the 3-D setups, `augment2d = true` that of the 2-D setups)")

@@ -950,6 +950,67 @@ int bsmi_aug2d_sample_nearest_u8(int device, const bsmi_aug2d_draw *draws, const
                                  const float *coords_dev, const int64_t frame_shape[2], const int64_t region_offset[2],
                                  const int64_t region_shape[2], const uint8_t *crops_dev, int64_t crop_pixels, uint8_t *out_dev, void *stream);
 
+/* ---- training augmentation of the 2-D setups: the intensity chain of raw, a whole batch per launch
+ * (csrc/augment2d_intensity.hip; reference models/2d_mtlsd/train.py:123-136 and its 2d_affs / 2d_lsd siblings: NoiseAugment ->
+ * IntensityAugment -> GammaAugment -> ImpulseNoiseAugment -> SmoothAugment -> DefectAugment under gp.Stack(10); the rules in
+ * full: DESIGN.md sections 7k and 7m, tests/aug2d_intensity_ref.py) ----
+ * The rule for draw s is the rule of the per-block chain above for the block (K, H, W) made of its K sections, unchanged --
+ * the same device code (csrc/augment_intensity.h), so the results are the same bits: the Philox counter is the voxel's
+ * linear index inside the draw's own stack, (k * H + y) * W + x; smoothing runs over all three axes of the stack, "reflect"
+ * across the K sections.  The batch x_dev is the trainer's float32 [K][S][H][W], changed in place: the sections of a draw
+ * are S planes apart.  Plane p = k * S + s; the per-plane tables scale_dev / shift_dev / gamma_dev (float32) and mode_dev
+ * (int32) have K * S entries, and stats_dev is bsmi_aug_section_stats_f32 of the batch taken as K * S sections (the planes
+ * are contiguous).  Each entry is ONE launch for all draws (smooth: two), grid.y over the planes, lanes along x; a draw
+ * whose bit for the node is clear is left bit-equal, and a call in which no draw has the node launches nothing.
+ *
+ *   sample_unit_f32_u8   aug2d_sample_f32_u8 with the table: a draw with BSMI_AUG2D_TOUCHED is written v / 255 (one rounded
+ *              division, the chain's input), every other draw exactly as aug2d_sample_f32_u8 writes it.
+ *   noise      sigma and seed of the draw.           impulse    seed and impulse_threshold (<= 2^32) of the draw.
+ *   intensity, gamma   the per-plane tables; rows of draws without the node are not read.
+ *   smooth     the draw's 2 * radius + 1 normalised taps at taps_offset floats inside taps_dev (taps_floats long); z pass
+ *              x_dev -> tmp_dev (a workspace of the batch's size; only the planes of smoothed draws are written and read),
+ *              then the LDS-tiled y/x pass back.
+ *   defect     mode per plane (`mode` in host memory is checked: 0 .. 3) for draws with BSMI_AUG2D_DEFECT; if final_map, then
+ *              x = 2 x - 1 for every draw with BSMI_AUG2D_TOUCHED.  The contrast scale is the draw's.
+ * The table is passed twice, as for the geometric chain: `idraws` in host memory, which every call checks (S < 1, K < 1,
+ * more than 65535 planes, bits outside the mask, a radius above BSMI_AUG_MAX_RADIUS, taps beyond taps_floats, a threshold
+ * above 2^32, K * S * H * W >= 2^31: BSMI_ERR_INVALID, nothing launched), and `idraws_dev`, the same bytes in device
+ * memory, which the kernels read. */
+#define BSMI_AUG2D_NOISE 1
+#define BSMI_AUG2D_INTENSITY 2
+#define BSMI_AUG2D_GAMMA 4
+#define BSMI_AUG2D_IMPULSE 8
+#define BSMI_AUG2D_SMOOTH 16
+#define BSMI_AUG2D_DEFECT 32
+#define BSMI_AUG2D_TOUCHED 64 /* some node changes the draw: resampled as v / 255, mapped 2 x - 1 at the end */
+typedef struct bsmi_aug2d_idraw {
+  uint64_t seed;              /* Philox key of noise and impulse */
+  uint64_t impulse_threshold; /* floor(q * 2^32) */
+  float noise_sigma;
+  float contrast_scale;
+  int32_t nodes;              /* mask of BSMI_AUG2D_* */
+  int32_t radius;             /* of the smoothing taps, 0 .. BSMI_AUG_MAX_RADIUS */
+  int32_t taps_offset;        /* of the draw's 2 * radius + 1 floats in the packed taps */
+  int32_t reserved[3];        /* 0; the struct is 48 bytes */
+} bsmi_aug2d_idraw;
+int bsmi_aug2d_sample_unit_f32_u8(int device, const bsmi_aug2d_draw *draws, const bsmi_aug2d_draw *draws_dev, const bsmi_aug2d_idraw *idraws,
+                                  const bsmi_aug2d_idraw *idraws_dev, int S, int K, const float *coords_dev, const int64_t frame_shape[2],
+                                  const int64_t region_offset[2], const int64_t region_shape[2], const uint8_t *crops_dev, int64_t crop_pixels,
+                                  float *out_dev, void *stream);
+int bsmi_aug2d_noise_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
+                         float *x_dev, void *stream);
+int bsmi_aug2d_intensity_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K,
+                             const int64_t shape[2], float *x_dev, const float *stats_dev, const float *scale_dev, const float *shift_dev,
+                             void *stream);
+int bsmi_aug2d_gamma_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
+                         float *x_dev, const float *stats_dev, const float *gamma_dev, void *stream);
+int bsmi_aug2d_impulse_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
+                           float *x_dev, void *stream);
+int bsmi_aug2d_smooth_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
+                          float *x_dev, float *tmp_dev, const float *taps_dev, int64_t taps_floats, void *stream);
+int bsmi_aug2d_defect_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
+                          float *x_dev, const float *stats_dev, const int32_t *mode, const int32_t *mode_dev, int final_map, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,18 @@
-"""Dev tool: the geometric augmentation of the 2-D setups on one GPU -> JSON lines.
+"""Dev tool: the geometric and the intensity augmentation of the 2-D setups on one GPU -> JSON lines.
 
 launches device-event ms of each of the four launches (after a warm-up, median of 9) at the shipped 2d_mtlsd shape: S = 10
          draws, K = 3 sections, input 196 x 196, output 104 x 104, an LSD context of 60 pixels at voxel size (40, 4, 4), so a
          frame of 224 x 224: aug2d_coords for ten full plans (lattice + shifts; including its three small uploads), raw over
          the input section, labels and mask over the labels window; with the bytes each launch must move and the rate that
          makes.
-source   batches/s of SectionSource alone on a synthetic Zarr store written here: plain and `augment2d`, wall clock.
-train    steps/s of a Trainer of the same setup fed through PrefetchSource with each of the two, alternating, and how long the
-         trainer waited for batches in each.
-`--only launches|source|train`; `--batches N` (default 40)."""
+intensity  the batched intensity chain at the same shape (ten plans that apply every node, sigma 1.5): device-event ms of each
+         launch and of the whole chain (median of 9), next to TEN calls of augment.apply_intensity on the ten stacks, the only way
+         to the same result without the batched launches.
+source   batches/s of SectionSource alone on a synthetic Zarr store written here: plain, `augment2d`, and `augment2d` with
+         `intensity = true`, wall clock.
+train    steps/s of a Trainer of the same setup fed through PrefetchSource: plain once, then `augment2d` and `augment2d` +
+         intensity alternating twice, and how long the trainer waited for batches in each.
+`--only launches|intensity|source|train`; `--batches N` (default 40)."""
 import argparse, json, os, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -63,6 +67,37 @@ def launches_part():
             "GB_per_s": {k: need[k] / ms[k] / 1e6 for k in ms}}
 
 
+def intensity_part():
+    from bootstrapper_amd import augment as G
+    rng = np.random.default_rng(0)
+    shape = (K,) + INPUT
+    lo, hi = G.gamma_interval((0.8, 1.2))
+    plans = [G.IntensityPlan(shape, noise_sigma=float(np.float32(0.1)), scale=rng.uniform(0.9, 1.1, K).astype(np.float32),
+                             shift=rng.uniform(-0.1, 0.1, K).astype(np.float32), gamma=G.gamma_exponent(rng.uniform(lo, hi, K)).astype(np.float32),
+                             impulse_threshold=2 ** 31, blur=1.5, weights=G.gaussian_weights(1.5), defect=np.array([3, 0, 0], dtype=np.int32),
+                             seed=int(rng.integers(0, 2 ** 64, dtype=np.uint64))) for _ in range(S)]
+    t = A.PackedIntensity2D(plans)
+    x0 = torch.rand((K, S) + INPUT, dtype=torch.float32, device="cuda")
+    x = x0.clone()
+    t.upload(x.device)
+    st, tmp = A.plane_stats(x), torch.empty_like(x)
+    ms = {"noise": events(lambda: A.noise2d(x, t)), "stats": events(lambda: A.plane_stats(x)), "intensity": events(lambda: A.intensity2d(x, t, st)),
+          "gamma": events(lambda: A.gamma2d(x, t, st)), "impulse": events(lambda: A.impulse2d(x, t)), "smooth": events(lambda: A.smooth2d(x, t, tmp)),
+          "defect": events(lambda: A.defect2d(x, t, st, True))}
+    stacks = [x0[:, s].contiguous() for s in range(S)]
+
+    def ten_calls():
+        for s in range(S):
+            G.apply_intensity(stacks[s], plans[s])
+
+    def fresh():   # the descriptor, per-plane and taps uploads are part of a batch's chain
+        return A.apply_intensity2d(x, A.PackedIntensity2D(plans))
+    chain = {"batched_chain": events(lambda: A.apply_intensity2d(x, t)), "batched_chain_with_packing_and_uploads": events(fresh),
+             "ten_calls_of_apply_intensity": events(ten_calls)}
+    return {"part": "intensity", "voxels": int(x.numel()), "launch_ms": ms, "chain_ms": chain,
+            "speedup_over_ten_calls": chain["ten_calls_of_apply_intensity"] / chain["batched_chain_with_packing_and_uploads"]}
+
+
 def write_store(root):
     from bootstrapper_amd.zarr_io import prepare_ds
     shape = (64, 512, 512)
@@ -76,7 +111,7 @@ def write_store(root):
     return {"samples": [{"raw": f"{root}/vol.zarr/raw", "labels": f"{root}/vol.zarr/labels"}], "voxel_size": list(VOXEL)}
 
 
-SOURCES = (("plain", False), ("augment2d", True))
+SOURCES = (("plain", False), ("augment2d", True), ("augment2d+intensity", {"intensity": True}))
 
 
 def source_part(cfg, batches):
@@ -103,7 +138,7 @@ def train_part(cfg, batches):
     settings = training_settings(NET)
     trainer = Trainer(model, settings["in_shape"], lr=settings["lr"])
     res = {"part": "train", "steps": batches, "runs": []}
-    for name, aug in SOURCES + SOURCES:   # alternating: the spread shows
+    for name, aug in SOURCES + SOURCES[1:]:   # alternating: the spread shows
         src = PrefetchSource(make_sample_source(dict(cfg, augment2d=aug), NET, 0, 0), 4, 0)
         try:
             for _ in range(3):
@@ -126,11 +161,13 @@ def train_part(cfg, batches):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["launches", "source", "train"])
+    ap.add_argument("--only", choices=["launches", "intensity", "source", "train"])
     ap.add_argument("--batches", type=int, default=40)
     a = ap.parse_args()
     if a.only in (None, "launches"):
         print(json.dumps(launches_part()), flush=True)
+    if a.only in (None, "intensity"):
+        print(json.dumps(intensity_part()), flush=True)
     if a.only in (None, "source", "train"):
         with tempfile.TemporaryDirectory() as root:
             cfg = write_store(root)

@@ -62,6 +62,7 @@ TRAIN_TENSORS = {"dout": 0, "gmask": 1, "gsplit": 2, "gsplit_hi": 3, "gsplit_lo"
 STEP_TYPES = ("input", "conv", "pool", "up", "head")
 CONV_FORMS = ("gather", "raster-halo", "box-halo", "halo-resident", "first-pass", "winograd F(2x2)", "winograd F(4x4)")
 STEP_FLAGS = {1: "fused-up", 2: "res-low", 4: "split-k"}
+STEP_BELOW_UP = 8  # reported as plan_steps()'s own key `below_up`, not among the flags
 
 
 class Codec(C.Structure):

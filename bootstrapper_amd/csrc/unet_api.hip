@@ -310,12 +310,33 @@ static bool wino_narrow_last(const bsmi_unet* h, const PassSite& p, int ci) {
   return wino_eligible(p, 0) && !wino_eligible(p, ci);
 }
 
+// Which first stages of a decoder pass behind a fused (1,2,2) upsampling convolve their upsampled source BELOW the upsampling
+// (PackedWino::below_*).  BSMI_CONV_BELOW_UP, read once per process: 0 = none (the F(4x4) form over both
+// sources, as before), 1 = every such stage, unset = the rule: every such stage as well, since both stages of the 128^3 block
+// that have the form gain by more than the spread of three repeats (ms per launch, tools/probe_unet.py bf16x3: 1800 -> 300
+// 4.51-4.55 -> 4.00-4.12, 360 -> 60 1.64 -> 1.05-1.07).  A stage that loses would be excluded here.
+static int conv_below_up_mode() {
+  static const int m = [] { const char* e = getenv("BSMI_CONV_BELOW_UP"); return e ? atoi(e) : -1; }();
+  return m;
+}
+static bool below_up_site(const bsmi_unet* h, const PassSite& p, int ci) {
+  if (conv_below_up_mode() == 0 || ci != 0 || p.nslots != 2 || p.nconv < 2 || !wino_eligible(p, 0)) return false;
+  if (&p < h->r_conv.data() || &p >= h->r_conv.data() + h->r_conv.size()) return false;
+  const int* f = h->cfg.downsample_factors[&p - h->r_conv.data()];
+  if (f[0] != 1 || f[1] != 2 || f[2] != 2) return false;   // what Planner::rec can fuse
+  if (p.cout <= 64 && !x3_fused_for(TILE_256x320)) return false;
+  return true;
+}
+
 static int pack_wino(bsmi_unet* h, PassSite& p, int ci) {
   PackedWino& pw = p.wino[ci];
   if (pw.w) { (void)hipFree(pw.w); pw.w = nullptr; }
   if (pw.res_w) { (void)hipFree(pw.res_w); pw.res_w = nullptr; }
   for (int part = 0; part < 2; ++part)
     if (pw.res_part_w[part]) { (void)hipFree(pw.res_part_w[part]); pw.res_part_w[part] = nullptr; }
+  if (pw.skip_w) { (void)hipFree(pw.skip_w); pw.skip_w = nullptr; }
+  if (pw.below_w) { (void)hipFree(pw.below_w); pw.below_w = nullptr; }
+  pw.below_ready = false;
   pw.ready = false;
   pw.fused_only = wino_narrow_last(h, p, ci);
   if (!wino_eligible(p, ci) && !pw.fused_only) return BSMI_OK;
@@ -409,6 +430,55 @@ static int pack_wino(bsmi_unet* h, PassSite& p, int ci) {
         if ((rc = pack_res(pw.res_part[part], &pw.res_part_w[part], &pw.res_part_lo[part]))) return rc;
       }
     }
+  }
+  if (below_up_site(h, p, ci) && pw.m == 4) {
+    // the skip connection alone in F(4x4) form: V holds its channels only
+    pw.skip_cin_of_v.assign(pw.cin_of_v.begin(), pw.cin_of_v.begin() + round_up(p.cin[0], kChanPad));
+    pw.skip_Cv = (int)pw.skip_cin_of_v.size();
+    wino_units(pw.skip_Cv, pw.skip_units);
+    size_t image_elems = 0, batch_elems = 0;
+    int rc = wino_pack_weights_dev(wm.data.data(), p.cout, cin_m, pw.skip_cin_of_v, pw.Npad, pw.skip_units, pw.m, &pw.skip_w, image_elems, batch_elems);
+    if (rc) return rc;
+    pw.skip_lo_image_bytes = image_elems * 2;
+    pw.skip_batch_bytes = batch_elems * 2;
+    // the upsampled source as nine (3,1,1) convolutions of the low-resolution tensor: K = its channels x kz (wino_units'
+    // order: 32-channel chunks, the three z taps inside a chunk), columns tap-major
+    const int cpad_low = round_up(p.cin[1], kChanPad), cpad_out = round_up(p.cout, kChanPad);
+    wino_units(cpad_low, pw.below_units);
+    pw.below_dense = p.cout <= 64;   // narrow stage: the nine taps side by side in one wide GEMM (9 Cpad columns on the 320-column tile)
+    pw.below_tile = pw.below_dense ? TILE_256x320 : pw.tile;
+    pw.below_Npad = pw.below_dense ? round_up(9 * cpad_out, tile_bn(pw.below_tile)) : pw.Npad;
+    const size_t nsteps = pw.below_units.size() / kUnitsPerStep;
+    const size_t tap_elems = nsteps * (size_t)pw.below_Npad * 32;
+    const size_t nelem = (pw.below_dense ? 1 : 9) * tap_elems + (size_t)kWeightRowSlack * 32;
+    std::vector<uint16_t> packed(2 * nelem, 0);
+    const bool dense = pw.below_dense;
+    const int cin1 = p.cin[1], cbase = p.cin[0];
+    host_parallel_for((size_t)p.cout, [&](size_t n_) {   // one output channel per task (pack_conv)
+      const int n = (int)n_;
+      for (size_t u = 0; u < pw.below_units.size(); ++u) {
+        const WinoUnit& un = pw.below_units[u];
+        if (un.dummy) continue;
+        const size_t s = u / kUnitsPerStep, j = u % kUnitsPerStep;
+        for (int kk = 0; kk < 16; ++kk) {
+          const int c = un.vc0 + kk;
+          if (c >= cin1) break;
+          const float* g = wm.data.data() + (((size_t)n * cin_m + (cbase + c)) * 3 + un.kz) * 9;  // [ky][kx]
+          for (int tap = 0; tap < 9; ++tap) {
+            const size_t idx = dense ? (s * pw.below_Npad + (size_t)tap * cpad_out + n) * 32 + j * 16 + kk
+                                     : (size_t)tap * tap_elems + (s * pw.below_Npad + n) * 32 + j * 16 + kk;
+            const uint16_t hi = host_f32_to_bf16(g[tap]);
+            packed[idx] = hi;
+            packed[nelem + idx] = host_f32_to_bf16(g[tap] - host_bf16_to_f32(hi));
+          }
+        }
+      }
+    });
+    pw.below_lo_image_bytes = nelem * 2;
+    pw.below_batch_bytes = dense ? 0 : tap_elems * 2;
+    BSMI_HIP(hipMalloc(&pw.below_w, packed.size() * 2));
+    BSMI_HIP(hipMemcpy(pw.below_w, packed.data(), packed.size() * 2, hipMemcpyHostToDevice));
+    pw.below_ready = true;
   }
   pw.ready = true;
   return BSMI_OK;
@@ -870,8 +940,11 @@ struct Planner {
       if (wants_fused) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: the upsampling was fused into this stage, which cannot take the Winograd form", p.prefix.c_str(), ci);
       return BSMI_OK;
     }
-    const int nsrc = ci == 0 ? p.nslots : 1;
-    const int Dv = o.D + 2, Ty = (o.H + wm - 1) / wm, Tx = (o.W + wm - 1) / wm, Cv = pw.Cv;   // F(4x4): the last tiles may overhang
+    // below-up: the upsampled source leaves the Winograd form (PackedWino::below_*); V holds the skip connection alone
+    const bool below = fuse_up && ci == 0 && pw.below_ready && wm == 4 && nsl == 2;
+    const int nsrc = below ? 1 : ci == 0 ? p.nslots : 1;
+    const std::vector<WinoUnit>& units = below ? pw.skip_units : pw.units;
+    const int Dv = o.D + 2, Ty = (o.H + wm - 1) / wm, Tx = (o.W + wm - 1) / wm, Cv = below ? pw.skip_Cv : pw.Cv;   // F(4x4): the last tiles may overhang
     const size_t vbatch = (size_t)Dv * Ty * Tx * Cv * 4;  // bytes of one batch of V: (hi, lo) pairs
     if (vbatch >= ((size_t)1 << 31)) {                     // 31-bit byte offsets inside a batch
       if (wants_fused) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: fused upsampling, but the transformed input is too large", p.prefix.c_str(), ci);
@@ -917,12 +990,12 @@ struct Planner {
       g.t[sl].sx = (int32_t)((int64_t)Cv * 4);
     }
     {
-      std::vector<KStep> ks(pw.units.size() / kUnitsPerStep);
+      std::vector<KStep> ks(units.size() / kUnitsPerStep);
       for (size_t s = 0; s < ks.size(); ++s) {
         KStep k;
         memset(&k, 0, sizeof k);
         for (int j = 0; j < kUnitsPerStep; ++j) {
-          const WinoUnit& u = pw.units[kUnitsPerStep * s + j];
+          const WinoUnit& u = units[kUnitsPerStep * s + j];
           if (!u.dummy) k.delta[j] = (int32_t)(((int64_t)u.kz * Ty * Tx * Cv + u.vc0) * 4);
         }
         ks[s] = k;
@@ -934,8 +1007,8 @@ struct Planner {
       g.steps = dks;
       g.nsteps = (int)ks.size();
     }
-    g.w = pw.w;
-    g.w_lo = (const char*)pw.w + pw.lo_image_bytes;
+    g.w = below ? pw.skip_w : pw.w;
+    g.w_lo = (const char*)g.w + (below ? pw.skip_lo_image_bytes : pw.lo_image_bytes);
     g.bias = pc.bias;
     g.out = Mbuf;
     g.Do = o.D; g.Ho = Ty; g.Wo = Tx; g.Co = o.Cpad;
@@ -945,7 +1018,65 @@ struct Planner {
     g.nbatch = nbatch;
     g.raw = 1;
     g.a_batch = (int64_t)vbatch;
-    g.w_batch = (int64_t)pw.batch_bytes;
+    g.w_batch = (int64_t)(below ? pw.skip_batch_bytes : pw.batch_bytes);
+    // below-up: Y[tap][z][i][j][n] = sum_{kz, c} W[n][c][kz][tap] L[z + kz + oz][i][j][c] over whole planes of the low-resolution
+    // tensor L, one raw launch: the nine taps as nine batches over the same rows, or side by side as columns (below_dense)
+    st.wino_has_below = false;
+    void* Ybuf = nullptr;
+    size_t Mbelow = 0;
+    int below_off[3] = {0, 0, 0};
+    if (below) {
+      const TDesc& lt = fuse_up->low;
+      for (int d = 0; d < 3; ++d) below_off[d] = so[1][d] + fuse_up->o[d];
+      if (fuse_up->f[1] != 2 || fuse_up->f[2] != 2 || lt.Cpad != slots[1].Cpad || below_off[0] < 0 || below_off[0] + o.D + 2 > lt.D || below_off[1] < 0 ||
+          below_off[2] < 0 || below_off[1] + o.H + 2 > 2 * lt.H || below_off[2] + o.W + 2 > 2 * lt.W)
+        BSMI_FAIL(BSMI_ERR_STATE, "%s: the low-resolution tensor does not cover the stage's input", p.prefix.c_str());
+      Mbelow = (size_t)o.D * lt.H * lt.W;
+      const size_t ybytes = 9 * Mbelow * o.Cpad * sizeof(float);
+      if (Mbelow * 9 >= ((size_t)1 << 31)) BSMI_FAIL(BSMI_ERR_STATE, "%s: too many rows of sums below the upsampling", p.prefix.c_str());
+      BSMI_HIP(hipMalloc(&Ybuf, ybytes));
+      plan->allocs.push_back(Ybuf);
+      plan->bytes += ybytes;
+      ConvArgs& r = st.wino_below;
+      memset(&r, 0, sizeof r);
+      for (int sl = 0; sl < kMaxConvTensors; ++sl) {
+        r.t[sl].base = (uint64_t)(uintptr_t)lt.ptr;
+        r.t[sl].sz = (int32_t)((int64_t)lt.H * lt.W * lt.Cpad * 4);
+        r.t[sl].sy = (int32_t)((int64_t)lt.W * lt.Cpad * 4);
+        r.t[sl].sx = (int32_t)((int64_t)lt.Cpad * 4);
+      }
+      std::vector<KStep> ks(pw.below_units.size() / kUnitsPerStep);
+      for (size_t s = 0; s < ks.size(); ++s) {
+        KStep k;
+        memset(&k, 0, sizeof k);
+        for (int j = 0; j < kUnitsPerStep; ++j) {
+          const WinoUnit& u = pw.below_units[kUnitsPerStep * s + j];
+          if (!u.dummy) k.delta[j] = (int32_t)(((int64_t)(u.kz + below_off[0]) * lt.H * lt.W * lt.Cpad + u.vc0) * 4);
+        }
+        ks[s] = k;
+      }
+      KStep* dks = nullptr;
+      BSMI_HIP(hipMalloc((void**)&dks, ks.size() * sizeof(KStep)));
+      plan->allocs.push_back(dks);
+      BSMI_HIP(hipMemcpy(dks, ks.data(), ks.size() * sizeof(KStep), hipMemcpyHostToDevice));
+      r.steps = dks;
+      r.nsteps = (int)ks.size();
+      r.w = pw.below_w;
+      r.w_lo = (const char*)pw.below_w + pw.below_lo_image_bytes;
+      r.bias = pc.bias;
+      r.out = Ybuf;
+      r.Do = o.D; r.Ho = lt.H; r.Wo = lt.W;
+      r.Co = pw.below_dense ? 9 * o.Cpad : o.Cpad;
+      r.M = (int)Mbelow;
+      r.Npad = pw.below_Npad;
+      r.relu = 0;
+      r.raw = 1;
+      r.nbatch = pw.below_dense ? 0 : 9;
+      r.a_batch = 0;
+      r.w_batch = (int64_t)pw.below_batch_bytes;
+      st.below_tile = pw.below_tile;
+      st.wino_has_below = true;
+    }
     // residual branch
     const bool last = ci == p.nconv - 1;
     const bool cut = fuse_up && last;  // the branch in two parts: the skip connection here, the upsampled map below the upsampling
@@ -1048,6 +1179,14 @@ struct Planner {
       wo.lf = fuse_up->f[1];
       wo.loz = low_off[0]; wo.loy = low_off[1]; wo.lox = low_off[2];
     }
+    if (below) {
+      wo.below = (const float*)Ybuf;
+      wo.btap = pw.below_dense ? (int64_t)o.Cpad : (int64_t)Mbelow * o.Cpad;
+      wo.brow = pw.below_dense ? 9 * o.Cpad : o.Cpad;
+      wo.boy = below_off[1]; wo.box = below_off[2];
+      wo.lD = fuse_up->low.D; wo.lH = fuse_up->low.H; wo.lW = fuse_up->low.W;
+      wo.lf = fuse_up->f[1];
+    }
     wo.bias = pc.bias;
     wo.out = o.ptr;
     wo.Do = o.D; wo.Ty = Ty; wo.Tx = Tx; wo.Co = o.Cpad;
@@ -1058,6 +1197,8 @@ struct Planner {
       st.exec_flops = 2.0 * (double)round_up((int)Mrows, 256) * pw.Npad * ((double)g.nsteps * kstep) * nbatch * 3.0;
       if (st.wino_has_res) st.exec_flops += 2.0 * (double)round_up(st.wino_res.M, 256) * pw.Npad * ((double)st.wino_res.nsteps * kstep) * 3.0;
       if (st.wino_has_res_low) st.exec_flops += 2.0 * (double)round_up(st.wino_res_low.M, 256) * pw.Npad * ((double)st.wino_res_low.nsteps * kstep) * 3.0;
+      if (st.wino_has_below)
+        st.exec_flops += 2.0 * (double)round_up(st.wino_below.M, 256) * pw.below_Npad * (pw.below_dense ? 1 : 9) * ((double)st.wino_below.nsteps * kstep) * 3.0;
     }
     st.tile = pw.tile;
     st.use_wino = true;
@@ -1598,6 +1739,8 @@ int bsmi_unet_destroy(bsmi_unet* h) {
       if (p.wino[c].res_w) (void)hipFree(p.wino[c].res_w);
       for (int part = 0; part < 2; ++part)
         if (p.wino[c].res_part_w[part]) (void)hipFree(p.wino[c].res_part_w[part]);
+      if (p.wino[c].skip_w) (void)hipFree(p.wino[c].skip_w);
+      if (p.wino[c].below_w) (void)hipFree(p.wino[c].below_w);
     }
   };
   for (auto& p : h->l_conv) free_site(p);
@@ -1829,6 +1972,7 @@ int bsmi_unet_forward(bsmi_unet* h, int precision, const void* raw_dev, int raw_
           if ((rc = launch_conv_igemm(st.wino_gemm, precision, st.tile, s, h->sk_ws, h->sk_grid))) break;
           if (st.wino_has_res && (rc = launch_conv_igemm(st.wino_res, precision, st.tile, s, h->sk_ws, h->sk_grid))) break;
           if (st.wino_has_res_low && (rc = launch_conv_igemm(st.wino_res_low, precision, st.tile, s, h->sk_ws, h->sk_grid))) break;
+          if (st.wino_has_below && (rc = launch_conv_igemm(st.wino_below, precision, st.below_tile, s, h->sk_ws, h->sk_grid))) break;
           rc = launch_wino_out(st.wino_out, s);
           break;
         }
@@ -1940,11 +2084,13 @@ int bsmi_unet_debug_step_info(bsmi_unet* h, int step, bsmi_unet_step_info* info,
       info->ksteps = st.wino_gemm.nsteps;
       bool up = false;
       for (int q = 0; q < st.wino_in.nsrc; ++q) up = up || st.wino_in.upf[q] > 0;
-      if (up || st.wino_out.low) info->flags |= BSMI_STEP_FUSED_UP;
+      if (up || st.wino_out.low || st.wino_has_below) info->flags |= BSMI_STEP_FUSED_UP;
+      if (st.wino_has_below) info->flags |= BSMI_STEP_BELOW_UP;
       if (st.wino_has_res_low) info->flags |= BSMI_STEP_RES_LOW;
       if (conv_igemm_split_k(st.wino_gemm, plan->prec, st.tile, sk_grid) ||
           (st.wino_has_res && conv_igemm_split_k(st.wino_res, plan->prec, st.tile, sk_grid)) ||
-          (st.wino_has_res_low && conv_igemm_split_k(st.wino_res_low, plan->prec, st.tile, sk_grid)))
+          (st.wino_has_res_low && conv_igemm_split_k(st.wino_res_low, plan->prec, st.tile, sk_grid)) ||
+          (st.wino_has_below && conv_igemm_split_k(st.wino_below, plan->prec, st.below_tile, sk_grid)))
         info->flags |= BSMI_STEP_SPLIT_K;
     } else if (st.use_h16) {
       info->form = BSMI_FORM_HALO_RESIDENT;

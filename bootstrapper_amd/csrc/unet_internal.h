@@ -78,6 +78,23 @@ struct PackedWino {
   std::vector<PackEntry> res_part[2];
   void* res_part_w[2] = {nullptr, nullptr};
   size_t res_part_lo[2] = {0, 0};
+  // The first stage of such a pass with its upsampled source convolved BELOW the upsampling (plan_wino, below-up): the
+  // interpolation weights do not depend on the channel, so tap (ky, kx) of the upsampled source is the interpolation of
+  // Y_(ky,kx) = the (3,1,1) convolution of the low-resolution tensor with W[:, :, :, ky, kx] -- nine GEMM column groups over
+  // the activation itself, no V for that source.  The skip connection keeps the F(4x4) form with a K of its own channels:
+  // `skip_*` are its transformed weights, `below_*` the nine-tap direct weights ([tap][K-step][Npad] when batched, columns
+  // tap * Cpad + n of one [K-step][Npad] image when dense).
+  bool below_ready = false;
+  std::vector<WinoUnit> skip_units, below_units;
+  std::vector<int> skip_cin_of_v;
+  int skip_Cv = 0;
+  void* skip_w = nullptr;
+  size_t skip_lo_image_bytes = 0, skip_batch_bytes = 0;
+  void* below_w = nullptr;
+  size_t below_lo_image_bytes = 0, below_batch_bytes = 0;
+  int below_Npad = 0;
+  bool below_dense = false;
+  TileCfg below_tile = TILE_256x320;
 };
 
 // Halo-resident form of a stage with at most 64 output channels in the split-bf16 mode (conv_h16.hip): its own K-step list --
@@ -135,6 +152,9 @@ struct PlanStep {
   WinoInArgs wino_in;
   ConvArgs wino_gemm, wino_res, wino_res_low;
   bool wino_has_res = false, wino_has_res_low = false;
+  ConvArgs wino_below;   // the upsampled source's nine-tap sums below the upsampling (PackedWino::below_*)
+  bool wino_has_below = false;
+  TileCfg below_tile = TILE_256x320;
   WinoOutArgs wino_out;
   TileCfg tile;
   TDesc in, out;

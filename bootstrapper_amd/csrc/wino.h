@@ -42,6 +42,14 @@ struct WinoOutArgs {
   // upsample_lf(low)[loz + z][loy + y][lox + x]
   const float* low;
   int lD, lH, lW, lf, loz, loy, lox;
+  // optional, m = 4 and lf = 2: the 3x3x3 taps of an upsampled source, convolved BELOW the upsampling.  Tap t = 3 ky + kx has raw
+  // sums Y_t[z][i][j][c] at below + t * btap + ((z * lH + i) * lW + j) * brow + c over whole low-resolution planes (lH x lW; z
+  // is the output's own); the transform adds, in raster order of the taps,
+  //   sum_t upsample_lf(Y_t)[z][boy + y + ky][box + x + kx]
+  // with lin_src's weights and clamping, after the bias and before the addend
+  const float* below;
+  int64_t btap;
+  int brow, boy, box;
   const float* bias;    // [>= Co]
   void* out;            // split-bf16 [Do][Ho][Wo][Co]
   int Do, Ty, Tx, Co;

@@ -610,7 +610,14 @@ __global__ __launch_bounds__(256, 2) void wino4_in_up_kernel(const WinoInArgs a,
 // one thread: the 4 x 4 output tile of 4 channels at (z, ty, tx); outputs past (Ho, Wo) -- overhanging tiles -- are not stored.
 // POOL (Ho, Wo even): the thread also stores the tile's 2 x 2 outputs of the (1,2,2) max-pool (WinoOutArgs::pool).  Rows and
 // columns leave the extent in pairs, so a pooled output is stored exactly when its four inputs are.
-template <bool LOW, bool POOL = false>
+// BELOW = 2 PY + PX >= 0 (WinoOutArgs::below; PY, PX: parities of boy, box): the thread first sums the nine taps' interpolated
+// low-resolution sums of its tile.  A tile's origin is even, so upsampled row u = 4 ty + boy + s, s = p + ky = 0 .. 5, is
+// 2 k0 + e with e = PY + s known at compile time: its source rows are k0 + (e >> 1) - 1 + (e & 1) and the next one -- fixed
+// places of a window of at most 4 rows per tap, loaded once per tile (4 x 4 vectors per tap instead of 4 per output and
+// tap), rows blended first, then columns.  Only the ADDRESSES are clamped to the plane; the weights are lin_src's, which
+// gives lin_src's value at the borders too (both neighbours of a clamped output fall on the same row).
+__device__ __forceinline__ constexpr int up2_rel(int e) { return (e >> 1) + (e & 1); }
+template <bool LOW, bool POOL = false, int BELOW = -1>
 __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, size_t total) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
@@ -623,6 +630,72 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
   const int z = (int)(t / a.Ty);
   const size_t Mrows = (size_t)a.Do * a.Ty * a.Tx;
   const size_t m = ((size_t)z * a.Ty + ty) * a.Tx + tx;
+  [[maybe_unused]] float bacc[4][4][4];  // BELOW: [p][q][channel]
+  if constexpr (BELOW >= 0) {
+    constexpr int PY = BELOW >> 1, PX = BELOW & 1;
+    const int uy = 4 * ty + a.boy, ux = 4 * tx + a.box;
+    const int wy_0 = (uy >> 1) - 1, wx_0 = (ux >> 1) - 1;  // window origin: row / column k0 - 1
+    float wy0[6], wy1[6], wx0[6], wx1[6];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+      int i0, i1;
+      lin_src(uy + s, 2, a.lH, i0, i1, wy0[s], wy1[s]);
+      lin_src(ux + s, 2, a.lW, i0, i1, wx0[s], wx1[s]);
+    }
+    uint32_t roff[5], coff[5];  // element offsets inside one plane of one tap (launch_wino_out: below 2^31)
+#pragma unroll
+    for (int r = 0; r < 5; ++r) {
+      const int y = wy_0 + r, x = wx_0 + r;
+      roff[r] = (uint32_t)(y < 0 ? 0 : (y > a.lH - 1 ? a.lH - 1 : y)) * (uint32_t)(a.lW * a.brow);
+      coff[r] = (uint32_t)(x < 0 ? 0 : (x > a.lW - 1 ? a.lW - 1 : x)) * (uint32_t)a.brow;
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) bacc[p][q][k] = 0.f;
+    const float* yb = a.below + (size_t)z * a.lH * a.lW * a.brow + 4 * cg;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const float* yt = yb + (size_t)(3 * ky + kx) * a.btap;
+        const int r_lo = up2_rel(PY + ky), nr = up2_rel(PY + ky + 3) + 2 - r_lo;  // rows r_lo .. r_lo + nr - 1, nr <= 4
+        const int c_lo = up2_rel(PX + kx), nc = up2_rel(PX + kx + 3) + 2 - c_lo;
+        f32x4_t win[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (r < nr && c < nc) win[r][c] = *(const f32x4_t*)(yt + (roff[r_lo + r] + coff[c_lo + c]));
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+          const int ra = up2_rel(PY + ky + p) - r_lo;
+          float rowb[4][4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c < nc) {
+#pragma unroll
+              for (int k = 0; k < 4; ++k) rowb[c][k] = wy0[ky + p] * win[ra][c][k] + wy1[ky + p] * win[ra + 1][c][k];
+            }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int ca = up2_rel(PX + kx + q) - c_lo;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) bacc[p][q][k] += wx0[kx + q] * rowb[ca][k] + wx1[kx + q] * rowb[ca + 1][k];
+          }
+        }
+        // one tap's window in flight at a time: the sums of this tap are pinned before the loads of the next one (left to
+        // itself the compiler issued the loads of all nine taps first and kept 144 vectors live: a scratch segment)
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(bacc[p][q][k]) : : "memory");
+      }
+  }
   float tp[6][4][4];  // tp[nu][p]: (A^T M)[p][nu]
 #pragma unroll
   for (int nu = 0; nu < 6; ++nu) {
@@ -660,6 +733,10 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
       float v[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) v[k] = y[q][k] + bv[k];
+      if constexpr (BELOW >= 0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] += bacc[p][q][k];
+      }
       if (a.addend) {
         const f32x4_t r0 = __builtin_nontemporal_load((const f32x4_t*)(a.addend + e));
 #pragma unroll
@@ -777,10 +854,21 @@ int launch_wino_out(const WinoOutArgs& a, hipStream_t s) {
   if (a.pool && (m != 4 || a.low || (Ho & 1) || (Wo & 1))) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: a pooled output needs F(4x4), even extents and no low-resolution residual");
   if (a.low && (a.lf < 1 || a.loz < 0 || a.loz + a.Do > a.lD || a.loy < 0 || a.loy + Ho > a.lH * a.lf || a.lox < 0 || a.lox + Wo > a.lW * a.lf))
     BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: the low-resolution residual does not cover the output");
+  if (a.below) {
+    if (m != 4 || a.lf != 2 || a.low || a.pool) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: sums below the upsampling need F(4x4), a factor of 2, no residual below it and no pooled output");
+    if (a.lH < 1 || a.lW < 1 || (int64_t)a.lH * a.lW * a.brow >= ((int64_t)1 << 31) || a.brow < a.Co || a.btap < a.Co || a.boy < 0 || a.box < 0 || a.boy + Ho + 2 > 2 * a.lH || a.box + Wo + 2 > 2 * a.lW)
+      BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: the sums below the upsampling do not cover the stage's input");
+  }
   const size_t total = (size_t)a.Do * a.Ty * a.Tx * (a.Co / (m == 4 ? 4 : 8));
   const dim3 grid((unsigned)((total + 255) / 256));
   if (m == 4) {
-    if (a.low) hipLaunchKernelGGL(wino4_out_kernel<true>, grid, dim3(256), 0, s, a, total);
+    if (a.below) {
+      const int par = 2 * (a.boy & 1) + (a.box & 1);
+      if (par == 0) hipLaunchKernelGGL((wino4_out_kernel<false, false, 0>), grid, dim3(256), 0, s, a, total);
+      else if (par == 1) hipLaunchKernelGGL((wino4_out_kernel<false, false, 1>), grid, dim3(256), 0, s, a, total);
+      else if (par == 2) hipLaunchKernelGGL((wino4_out_kernel<false, false, 2>), grid, dim3(256), 0, s, a, total);
+      else hipLaunchKernelGGL((wino4_out_kernel<false, false, 3>), grid, dim3(256), 0, s, a, total);
+    } else if (a.low) hipLaunchKernelGGL(wino4_out_kernel<true>, grid, dim3(256), 0, s, a, total);
     else if (a.pool) hipLaunchKernelGGL((wino4_out_kernel<false, true>), grid, dim3(256), 0, s, a, total);
     else hipLaunchKernelGGL(wino4_out_kernel<false>, grid, dim3(256), 0, s, a, total);
   } else if (a.low) hipLaunchKernelGGL(wino_out_kernel<true>, grid, dim3(256), 0, s, a, total);

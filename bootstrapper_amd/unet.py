@@ -247,7 +247,8 @@ class Model:
         """The launches of the last forward's plan, in order, as dicts: type (input / conv / pool / up / head), whether the
         forward materialised the step's output (debug_activation refuses the others), shape (D, H, W, C); conv steps also
         carry the state-dict prefix of their ConvPass, the conv index inside it, the kernel form that ran, its flags
-        (fused-up, res-low, split-k), the GEMM tile's BN and the K-step count."""
+        (fused-up, res-low, split-k), the GEMM tile's BN and the K-step count, and below_up: whether the stage convolves its
+        upsampled source below the upsampling (csrc/unet_api.hip below_up_site)."""
         n = C.c_int()
         check(lib.bsmi_unet_debug_step_info(self._h, 0, None, C.byref(n)))
         out = []
@@ -257,7 +258,8 @@ class Model:
             d = {"step": i, "type": _lib.STEP_TYPES[si.type], "materialised": bool(si.materialised), "shape": tuple(si.shape)}
             if d["type"] == "conv":
                 d.update(prefix=si.prefix.decode(), conv=si.conv_index, form=_lib.CONV_FORMS[si.form],
-                         flags=tuple(name for bit, name in _lib.STEP_FLAGS.items() if si.flags & bit), bn=si.bn, ksteps=si.ksteps)
+                         flags=tuple(name for bit, name in _lib.STEP_FLAGS.items() if si.flags & bit), bn=si.bn, ksteps=si.ksteps,
+                         below_up=bool(si.flags & _lib.STEP_BELOW_UP))
             elif d["type"] == "head":
                 d.update(prefix=si.prefix.decode(), head=si.head)
             elif d["type"] in ("pool", "up"):

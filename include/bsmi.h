@@ -330,7 +330,8 @@ enum {
 enum {
   BSMI_STEP_FUSED_UP = 1,      /* a source is read through an on-the-fly upsampling (the UP step before it is not materialised) */
   BSMI_STEP_RES_LOW = 2,       /* part of the residual branch runs as a GEMM of its own below the upsampling */
-  BSMI_STEP_SPLIT_K = 4        /* the launcher's rule sends (one of) the GEMM launches of this step to the persistent split-K form */
+  BSMI_STEP_SPLIT_K = 4,       /* the launcher's rule sends (one of) the GEMM launches of this step to the persistent split-K form */
+  BSMI_STEP_BELOW_UP = 8       /* the 3x3x3 taps of the upsampled source run as nine (3,1,1) GEMM column groups below the upsampling */
 };
 typedef struct {
   int32_t type;          /* BSMI_STEP_* */

@@ -46,7 +46,7 @@ struct Elem<bf16_elem> {
 };
 
 // Element of a split-bf16 tensor (BSMI_PREC_BF16X3): the kernels multiply bf16 planes exactly as in the bf16 mode --
-// the host lists every logical K-step three times (hi x hi, lo x hi, hi x lo: unet_api.hip) -- and the epilogue
+// the host lists every logical K-step three times (hi x hi, lo x hi, hi x lo: Planner::pass of unet_plan.hip) -- and the epilogue
 // writes the f32 result as a (hi, lo) pair of planes: hi = bf16(v), lo = bf16(v - hi).
 struct bf16s_elem {
   uint16_t v;

@@ -93,7 +93,7 @@ enum PackSet {
 };
 // F32_LAZY leaves out the f32 weight image of a forward launch that runs in its split-bf16 form during training
 // (PackJob::shadowed); the images are then stale until train_refresh_f32_images, which an f32 inference call on the same
-// handle triggers (unet_api.hip) -- the bias images and everything the step itself reads are always current.
+// handle triggers (bsmi_unet_forward, unet_forward.hip) -- the bias images and everything the step itself reads are always current.
 enum PackF32 { F32_CURRENT, F32_LAZY };
 
 struct ConvBwd {  // backward data of one CONV plan step

@@ -1,6 +1,16 @@
-// Internal structures of the U-Net engine shared by unet_api.hip (planner, forward) and the training engine (train*.hip: backward,
+// Internal structures of the U-Net engine shared by its translation units and the training engine (train*.hip: backward,
 // optimizer; its own structures are in train_internal.h).  Not part of the C ABI.
+//   unet_api.hip        the error string, the handle's life cycle (create, load_weight, finalize, destroy), shape / flop queries,
+//                       the stream and persistent-grid entry points
+//   unet_rules.hip      which stage takes which kernel form: the BSMI_* switches and the predicates, with their measurements
+//   unet_pack.hip       unit lists (build_entries) and weight images of every form (pack_conv, pack_wino, pack_h16), their release
+//   unet_plan.hip       the planner (unet_plan.h): the walk over the network, the direct forms of a stage, the plan cache
+//   unet_plan_wino.hip  the Winograd form of a stage, one function per launch
+//   unet_forward.hip    bsmi_unet_forward (the walk over a plan), the forward chain, the profiling events and entry points
+//   unet_debug.hip      bsmi_unet_debug_activation, bsmi_unet_debug_step_info
+// The kernels are in conv_*.hip, wino.hip, first_pass.hip and unet_ops.hip.
 #pragma once
+#include <cstring>
 #include <map>
 #include <memory>
 #include <string>
@@ -199,11 +209,26 @@ struct Plan {
 
 struct TrainState;
 
+static inline uint16_t host_f32_to_bf16(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);  // NaN stays NaN
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+static inline float host_bf16_to_f32(uint16_t b) {
+  const uint32_t u = (uint32_t)b << 16;
+  float f;
+  memcpy(&f, &u, 4);
+  return f;
+}
+
+// ---- unet_pack.hip ----
 int esize(int prec);  // bytes of one stored element (per plane in the split mode)
 int ksplit(int prec); // K-steps the kernel walks per logical K-step (3 in the split-bf16 mode)
 int bke(int prec);   // elements per K-step row
 int sube(int prec);  // elements per 32-byte unit
-// unit list of stage `ci` of a ConvPass (see unet_api.hip)
+// unit list of stage `ci` of a ConvPass
 void build_entries(const PassSite& p, int ci, int prec, std::vector<PackEntry>& out, std::vector<PackPhase>* phases_out = nullptr);
 
 }  // namespace bsmi
@@ -238,8 +263,36 @@ struct bsmi_unet {
 };
 
 namespace bsmi {
+// weight images of stage `ci` of ConvPass `p` (pack_wino / pack_h16: the split-bf16 mode's forms, where the rules give the stage one)
+int pack_conv(bsmi_unet* h, PassSite& p, int ci, int prec);
+int pack_wino(bsmi_unet* h, PassSite& p, int ci);
+int pack_h16(bsmi_unet* h, PassSite& p, int ci);
+// frees a form's device images and marks it not ready
+void release(PackedConv& pc);
+void release(PackedWino& pw);
+void release(PackedH16& ph);
+
+// ---- unet_rules.hip ----
+bool x3_fused_for(TileCfg tile);
+bool wino_eligible(const PassSite& p, int ci);
+int wino_tile_edge();
+bool wino_narrow_last(const bsmi_unet* h, const PassSite& p, int ci);
+bool below_up_site(const bsmi_unet* h, const PassSite& p, int ci);
+bool fuse_up_enabled();
+bool pool_fuse_enabled();
+int h16_mode();
+int h16_only_npad();
+bool h16_balanced();
+bool rh_enabled(int prec, TileCfg tile, size_t nsteps);
+bool box_enabled();
+bool first_pass_eligible(const bsmi_unet* h);
+
+// ---- unet_plan.hip ----
+int check_shape_arg(const int64_t s[3]);
 // the cached launch plan of (precision, input shape); built on first use
 int get_plan(bsmi_unet* h, int precision, const int64_t in_shape[3], Plan** out);
+int dry_plan(bsmi_unet* h, const int64_t in_shape[3], Plan& plan);  // shapes and FLOPs only: nothing allocated, no device touched
+void free_plan(Plan* p);
 void free_train_state(bsmi_unet* h);
 int train_forward_conv_x3(bsmi_unet* h, const PlanStep& st, hipStream_t s);  // train_plan.hip
 int train_refresh_f32_images(bsmi_unet* h, hipStream_t s);  // train_pack.hip: f32 weight images left stale by the last optimizer step

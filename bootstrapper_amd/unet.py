@@ -248,7 +248,7 @@ class Model:
         forward materialised the step's output (debug_activation refuses the others), shape (D, H, W, C); conv steps also
         carry the state-dict prefix of their ConvPass, the conv index inside it, the kernel form that ran, its flags
         (fused-up, res-low, split-k), the GEMM tile's BN and the K-step count, and below_up: whether the stage convolves its
-        upsampled source below the upsampling (csrc/unet_api.hip below_up_site)."""
+        upsampled source below the upsampling (csrc/unet_rules.hip below_up_site)."""
         n = C.c_int()
         check(lib.bsmi_unet_debug_step_info(self._h, 0, None, C.byref(n)))
         out = []

@@ -5,7 +5,7 @@ compares the output with a float64 computation of that one operation on the inpu
 tests/test_layers_cpu.py runs the same comparison on synthetic stages with emulations (and faulty emulations) of
 the kernels' arithmetic in the kernel's place.  This module holds what both share:
 
-  walk()            the planner's list of operations (Planner::run / rec / pass of csrc/unet_api.hip), from a net config
+  walk()            the planner's list of operations (Planner::run / rec / pass of csrc/unet_plan.hip), from a net config
   Dense / Upsampled tensors that hand out voxels as float64 rows (an upsampled map that the forward never writes is
                     the reference upsampling of the device's low-resolution map, evaluated only where it is read)
   Stage             one conv launch in its GEMM view: out[m, n] = relu(sum_k X[m, k] W[k, n] + b[n]), K = (source, tap,
@@ -332,7 +332,7 @@ class Stage:
 
     # -- the accumulation allowance ---------------------------------------------------------------------------------------
     def ksteps(self, prec, wino=False):
-        """Column indices of K, K-step by K-step, in the order the kernel walks them (build_entries of unet_api.hip: per
+        """Column indices of K, K-step by K-step, in the order the kernel walks them (build_entries of unet_pack.hip: per
         source, chunks of one K-step's channels with the taps inside -- a source of at most one unit's channels pairs two
         x-adjacent taps per K-step --, then the residual's chunks; Winograd (wino_units): per 32-channel chunk the three z
         taps, a K-step being the in-plane taps of one z tap in the transform domain)."""

@@ -1,4 +1,4 @@
-"""Convolving below the upsampling (csrc/unet_api.hip plan_wino below-up, csrc/wino.hip wino4_out_kernel<.., BELOW>), restated
+"""Convolving below the upsampling (csrc/unet_plan_wino.hip WinoStage::below_up, csrc/wino.hip wino4_out_kernel<.., BELOW>), restated
 in float64 with the output transform's index contract.  Needs no GPU.
 
 For U = up(1,2,2)(L) (torch's trilinear upsampling, align_corners = False) and a 3x3x3 kernel W,

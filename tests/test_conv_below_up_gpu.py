@@ -1,5 +1,5 @@
 """The first stage of a decoder ConvPass behind a fused (1,2,2) upsampling with its upsampled source convolved BELOW the
-upsampling (csrc/unet_api.hip below_up_site, csrc/wino.hip wino4_out_kernel<.., BELOW>): the skip connection stays in F(4x4)
+upsampling (csrc/unet_rules.hip below_up_site, csrc/wino.hip wino4_out_kernel<.., BELOW>): the skip connection stays in F(4x4)
 form, the nine in-plane taps of the upsampled source are nine (3,1,1) GEMM column groups over the low-resolution tensor, and
 the output transform interpolates and adds them.  BSMI_CONV_BELOW_UP=0 restores the F(4x4) form over both sources,
 BSMI_FUSE_UP=0 turns every fusion off.  Needs an MI355X; every switch is read once per process, so each configuration runs in
@@ -55,7 +55,7 @@ _STOP = []
 
 
 def RULE(cin_low, cout):
-    """csrc/unet_api.hip below_up_site, the default rule: which first stages behind a fused upsampling take the form"""
+    """csrc/unet_rules.hip below_up_site, the default rule: which first stages behind a fused upsampling take the form"""
     return True
 
 

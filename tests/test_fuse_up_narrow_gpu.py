@@ -1,4 +1,4 @@
-"""The decoder rule of csrc/unet_api.hip wino_narrow_last: behind a (1,2,2) upsampling the narrow last stage of a decoder
+"""The decoder rule of csrc/unet_rules.hip wino_narrow_last: behind a (1,2,2) upsampling the narrow last stage of a decoder
 ConvPass takes the Winograd form whenever the pass's first stage does, so that Planner::rec fuses the upsampling into the pass
 (the map is never written).  BSMI_FUSE_UP_NARROW=0 restores the rule before it, BSMI_FUSE_UP=0 turns every fusion off.  Needs
 an MI355X; every switch is read once per process, so each configuration runs in a child process.

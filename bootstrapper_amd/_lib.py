@@ -258,6 +258,10 @@ def _load():
         "bsmi_aug2d_impulse_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp]),
         "bsmi_aug2d_smooth_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, vp, C.c_int64, vp]),
         "bsmi_aug2d_defect_f32": (i32, [i32, C.POINTER(Aug2dIDraw), vp, i32, i32, i64p, vp, vp, C.POINTER(C.c_int32), vp, i32, vp]),
+        "bsmi_augin_group_mean_f32": (i32, [i32, i64p, vp, vp, i32, vp, vp]),
+        "bsmi_augin_intensity_f32": (i32, [i32, i64p, vp, vp, vp, vp, i32, vp]),
+        "bsmi_augin_smooth_f32": (i32, [i32, i64p, vp, vp, vp, vp, i32, vp]),
+        "bsmi_augin_contrast_f32": (i32, [i32, i64p, vp, vp, vp, C.c_float, vp]),
         # include/bsmi_io.h
         "bsmi_codec_bound": (C.c_size_t, [C.POINTER(Codec), C.c_size_t]),
         "bsmi_codec_decode": (i32, [C.POINTER(Codec), vp, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -290,3 +294,7 @@ def check(rc):
 
 def i64x3(v):
     return (C.c_int64 * 3)(*[int(x) for x in v])
+
+
+def i64x4(v):
+    return (C.c_int64 * 4)(*[int(x) for x in v])

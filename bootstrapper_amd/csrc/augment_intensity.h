@@ -88,8 +88,9 @@ __device__ __forceinline__ float tap_sum(int radius, W w, At at) {
 }
 
 // The y and x passes of one kTileY x kTileX output tile of the plane `sec` (H x W), staged with its halo in LDS: y into `mid`
-// (halo columns included), x out of it into `dst` (the same plane of the output).  256 threads; w: 2 r + 1 taps.
-template <class W>
+// (halo columns included), x out of it into `dst` (the same plane of the output).  256 threads; w: 2 r + 1 taps.  kClip holds
+// the result to [0, 1], which the exact sum never leaves (the float32 taps can add up to 1 and a few ulp).
+template <bool kClip = false, class W>
 __device__ __forceinline__ void smooth_yx_tile(int H, int W_, int r, W w, const float* __restrict__ sec, float* __restrict__ dst) {
   constexpr int kCols = kTileX + 2 * kMaxRadius + 1;   // + 1: rows start on different banks
   __shared__ float tile[kTileY + 2 * kMaxRadius][kCols];
@@ -108,8 +109,10 @@ __device__ __forceinline__ void smooth_yx_tile(int H, int W_, int r, W w, const 
   __syncthreads();
   const int tx = threadIdx.x % kTileX, x = x0 + tx;
   if (x >= W_) return;
-  for (int ly = threadIdx.x / kTileX; ly < kTileY && y0 + ly < H; ly += 256 / kTileX)
-    dst[(size_t)(y0 + ly) * W_ + x] = tap_sum(r, w, [&](int k) { return mid[ly][tx + k]; });
+  for (int ly = threadIdx.x / kTileX; ly < kTileY && y0 + ly < H; ly += 256 / kTileX) {
+    const float v = tap_sum(r, w, [&](int k) { return mid[ly][tx + k]; });
+    dst[(size_t)(y0 + ly) * W_ + x] = kClip ? clip01(v) : v;
+  }
 }
 
 }  // namespace augi

@@ -20,7 +20,9 @@ models/2d_mtlsd/train.py:112-122 runs on the whole batch first, one coordinate l
 for the ten draws (augment2d.py, csrc/augment2d.hip; specified rules, section 7l), and with `intensity` inside that table the
 intensity nodes of raw after it, one launch per node for the ten draws (csrc/augment2d_intensity.hip; section 7m).
 `SyntheticSource` feeds the second-stage setups (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
-`synthetic_labels = true` in the train config.  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
+`synthetic_labels = true` in the train config; with `input_augment` beside it every input array runs through the reference's degradation of
+the inputs (noise, intensity per channel and per section, smoothing per section, low contrast: augment_inputs.py, csrc/augment_inputs.hip;
+specified rules, section 7n).  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
 """
 import ctypes as C
 import glob
@@ -604,13 +606,22 @@ class SyntheticSource:
     draws come from one random.Random(seed) stream, so one seed gives one sequence of batches, bit for bit.
     Batch: raw (1, C, D, H, W) = the inputs concatenated in net_config["inputs"] order; gt_affs / affs_weights (K, d, h, w).
 
-    NOT built (logged by run_training): SimpleAugment, DeformAugment, ShiftAugment of the labels and the Noise / Intensity /
-    Smooth / Defect augmentations of the inputs."""
+    input_augment: an augment_inputs.InputAugParams (or True for the reference's arguments) degrades every input array the way
+    the reference's train.py does ("simulate noisy defected predictions": noise, intensity per channel and per section,
+    smoothing per section, low contrast; augment_inputs.py, csrc/augment_inputs.hip), in place, after the
+    batch is made.  Its plans come from a stream of their own, np.random.default_rng((seed, 1)), one plan per input array in
+    net_config["inputs"] order: the random.Random(seed) stream is not touched, so gt_affs and affs_weights are those of the
+    un-augmented source batch by batch, and so is raw where no node of a plan is applied.  None (the default): today's batches.
+
+    NOT built (logged by run_training): SimpleAugment, DeformAugment, ShiftAugment of the labels; without `input_augment` also
+    the Noise / Intensity / Smooth / Defect augmentations of the inputs."""
 
     NOT_BUILT = ("SimpleAugment, DeformAugment and ShiftAugment of the labels; NoiseAugment, IntensityAugment, SmoothAugment and "
                  "DefectAugment of the inputs")
+    NOT_BUILT_WITH_INPUT_AUGMENT = ("SimpleAugment, DeformAugment and ShiftAugment of the labels; DefectAugment's missing, deformed and "
+                                    "artifact sections of the inputs (0 / absent in the reference's call)")
 
-    def __init__(self, net_config, voxel_size=(1, 1, 1), device=0, seed=42):
+    def __init__(self, net_config, voxel_size=(1, 1, 1), device=0, seed=42, input_augment=None):
         from .synth_labels import anisotropy_range
         ins = net_config.get("inputs", {})
         keys = set(ins)
@@ -635,6 +646,15 @@ class SyntheticSource:
         self.device = int(device)
         self.rng = random.Random(seed)
         self.engine = None   # made by the first batch: the constructor touches no GPU
+        self.arrays, at = [], 0   # (input, first channel, channel after the last) of every input array inside raw
+        for key, spec in self.inputs:
+            self.arrays.append((key, at, at + int(spec["dims"])))
+            at += int(spec["dims"])
+        if input_augment is True:
+            from .augment_inputs import InputAugParams
+            input_augment = InputAugParams()
+        self.input_augment = input_augment
+        self.aug_rng = np.random.default_rng((int(seed), 1)) if input_augment is not None else None
 
     def __iter__(self):
         return self
@@ -676,6 +696,14 @@ class SyntheticSource:
         raw = torch.cat([self._input(key, spec, obf) for key, spec in self.inputs], dim=0)[None].contiguous()
         ctx = [(i - o) // 2 for i, o in zip(self.inp, self.out)]
         affs, weights = affinity_targets_roi(lab[None].contiguous(), None, ctx, self.out, self.out_nhood, self.out_grow, only_xy=True)
+        if self.input_augment is not None:
+            from .augment_inputs import apply_inputs, draw_input_plan
+            if tuple(raw.shape[1:]) != (self.arrays[-1][2], *self.inp):
+                raise RuntimeError(f"raw of shape {tuple(raw.shape)} does not hold the inputs' {self.arrays[-1][2]} channels of {self.inp}")
+            for _, lo, hi in self.arrays:
+                plan = draw_input_plan(self.aug_rng, self.input_augment, (hi - lo, *self.inp))
+                if plan.applied:
+                    apply_inputs(raw[0, lo:hi], plan)   # a contiguous channel range of the batch, changed in place
         return {"raw": raw, "gt_affs": affs[:, 0].contiguous(), "affs_weights": weights[:, 0].contiguous()}
 
 
@@ -783,12 +811,20 @@ def make_sample_source(config, net_config, device=0, rank=0):
     if augment2d is not None and (set(net_config.get("inputs", {"raw": None})) != {"raw"} or not outs or set(outs) - {"2d_affs", "2d_lsds"}):
         raise NotImplementedError(f"augment2d: not built for the {setup_name(net_config)} setup; it covers 2d_affs, 2d_lsd and 2d_mtlsd "
                                   "(the first-stage 3-D setups have the key `augment`)")
-    if set(net_config.get("inputs", {"raw": None})) != {"raw"}:
+    from .augment_inputs import InputAugParams
+    input_augment = InputAugParams.from_config(config.get("input_augment"))
+    second_stage = set(net_config.get("inputs", {"raw": None})) != {"raw"}
+    if input_augment is not None and not (second_stage and config.get("synthetic_labels", False)):
+        raise NotImplementedError(f"input_augment: not built for the {setup_name(net_config)} setup" + ("" if second_stage else
+                                  " (its raw has the keys `augment` and `augment2d` with `intensity` inside)") + "; it degrades the inputs "
+                                  "of the second-stage setups (3d_affs_from_2d_lsd, _2d_affs, _2d_mtlsd, _3d_lsd) and goes together with "
+                                  "`synthetic_labels = true`")
+    if second_stage:
         if not config.get("synthetic_labels", False):
             raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
                                       "the built-in sample source makes only when the train config sets `synthetic_labels = true`; "
                                       "without it it feeds 2d_affs, 2d_lsd, 2d_mtlsd, 3d_affs, 3d_lsd and 3d_mtlsd")
-        return SyntheticSource(net_config, config.get("voxel_size", (1, 1, 1)), device=device, seed=42 + int(rank))
+        return SyntheticSource(net_config, config.get("voxel_size", (1, 1, 1)), device=device, seed=42 + int(rank), input_augment=input_augment)
     if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
         s = training_settings(net_config)
         return SectionSource(config["samples"], net_config["input_shape"], net_config["output_shape"], int(net_config.get("adj_slices", 1)),
@@ -903,7 +939,11 @@ def run_training(config_file, device=0, batches=None, log=print):
             log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
                 "(`augment = true` turns on the geometric chain of the 3-D setups, `augment2d = true` that of the 2-D setups)")
         batches = make_sample_source(config, net_config, device, rank)
-        if isinstance(batches, SyntheticSource):
+        if isinstance(batches, SyntheticSource) and batches.input_augment is not None:
+            from .augment_inputs import NODES
+            log(f"note: synthetic labels (synthetic_labels = true) with the input augmentation on the device ({NODES}: `input_augment`); "
+                f"not built: {SyntheticSource.NOT_BUILT_WITH_INPUT_AUGMENT}")
+        elif isinstance(batches, SyntheticSource):
             log(f"note: synthetic labels (synthetic_labels = true); not built: {SyntheticSource.NOT_BUILT}")
         depth = int(config.get("prefetch", 4))   # an addition to the reference's train config: batches kept ready (0: inline)
         if depth > 0:

@@ -1012,6 +1012,46 @@ int bsmi_aug2d_smooth_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi
 int bsmi_aug2d_defect_f32(int device, const bsmi_aug2d_idraw *idraws, const bsmi_aug2d_idraw *idraws_dev, int S, int K, const int64_t shape[2],
                           float *x_dev, const float *stats_dev, const int32_t *mode, const int32_t *mode_dev, int final_map, void *stream);
 
+/* ---- training augmentation of the second-stage inputs (csrc/augment_inputs.hip; reference models/3d_affs_from_2d_mtlsd/
+ * train.py:110-126 and its three siblings, "simulate noisy defected predictions": NoiseAugment -> IntensityAugment per channel
+ * -> IntensityAugment per section -> SmoothAugment per section -> DefectAugment (low contrast only); the rules in full:
+ * DESIGN.md section 7n, tests/augin_ref.py) ----
+ * Specified rules, like the chains above: parity with gunpowder is in distribution.  One input array is a float32
+ * x_dev [C][D][H][W] with values in [0, 1], changed in place; channels are axis 0, sections (the z planes) axis 1, and plane
+ * p = c * D + z is H * W contiguous floats.  Each node is one call; a node the caller's plan skips is simply not called.
+ * Stateless, asynchronous on `stream`; fewer than 2^31 voxels, at most 65535 planes (BSMI_ERR_INVALID otherwise).  The
+ * per-voxel arithmetic is that of the intensity chain of raw (csrc/augment_intensity.h), the same device code.
+ *
+ *   noise      bsmi_aug_noise_f32 on the array taken as [C * D][H][W]: the Philox counter is the linear index within the
+ *              array, ((c * D + z) * H + y) * W + x, so every channel has its own noise.  No entry of its own.
+ *   group_mean mean_dev [C] (axis 0: of every channel over its D, H, W) or [D] (axis 1: of every section over C, H, W).
+ *              Deterministic, no atomics: the sum of every plane is taken as bsmi_aug_section_stats_f32 takes it on
+ *              [C * D][H][W] (BSMI_AUG_STAT_PARTS fixed chunks in a fixed order, combined in index order) and divided by
+ *              H * W; a group's mean then adds the means of its planes in index order (z = 0 .. D - 1 of the channel, c = 0 ..
+ *              C - 1 of the section) and divides by their number.  workspace_dev: BSMI_AUGIN_WORKSPACE_FLOATS(C, D) floats.
+ *   intensity  x = clip(m_g + (x - m_g) * scale_g + shift_g, 0, 1), g the voxel's channel (axis 0) or section (axis 1);
+ *              mean_dev, scale_dev, shift_dev: float32 [C] or [D].
+ *   smooth     per section z a separable Gaussian with the section's own normalised taps, weights_dev [D][2 *
+ *              BSMI_AUG_MAX_RADIUS + 1] float32 (the first 2 * radius_dev[z] + 1 of a row are read) and radius_dev [D] int32,
+ *              border "reflect" (d c b a | a b c d, repeated where the radius exceeds the axis); passes along c (x_dev ->
+ *              tmp_dev, a workspace of the array's size; a thread holds its column's C values, C <= BSMI_AUGIN_MAX_CHANNELS),
+ *              then y and x (one launch, from a tile staged with its halo in LDS, tmp_dev -> x_dev); each tap sum runs from
+ *              tap 0 upwards, and the last one is held to [0, 1], which the exact sum never leaves (the float32 taps can add
+ *              up to 1 and a few ulp).  channels = 0 makes the c pass a copy.  A section of radius 0 is touched by neither launch; the
+ *              kernels hold a radius to 0 .. BSMI_AUG_MAX_RADIUS, so no table takes them beyond their tiles.
+ *   contrast   mode_dev int32 [D]: a section of mode 3 becomes x = m_z + (x - m_z) * contrast_scale with m_z = mean_dev[z]
+ *              (group_mean, axis 1); every other section is not touched. */
+#define BSMI_AUGIN_MAX_CHANNELS 16
+#define BSMI_AUGIN_WORKSPACE_FLOATS(C, D) ((size_t)(C) * (D) * (BSMI_AUG_STAT_PARTS * 3 + 3))
+int bsmi_augin_group_mean_f32(int device, const int64_t shape[4], const float *x_dev, float *workspace_dev, int axis, float *mean_dev,
+                              void *stream);
+int bsmi_augin_intensity_f32(int device, const int64_t shape[4], float *x_dev, const float *mean_dev, const float *scale_dev,
+                             const float *shift_dev, int axis, void *stream);
+int bsmi_augin_smooth_f32(int device, const int64_t shape[4], float *x_dev, float *tmp_dev, const float *weights_dev, const int32_t *radius_dev,
+                          int channels, void *stream);
+int bsmi_augin_contrast_f32(int device, const int64_t shape[4], float *x_dev, const float *mean_dev, const int32_t *mode_dev,
+                            float contrast_scale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

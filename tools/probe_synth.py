@@ -7,7 +7,10 @@ stages   device-event ms per stage (after a warm-up, median of 5) at the referen
 source   batches/s of SyntheticSource alone (its own draws: the branches and anisotropies as they come), wall clock.
 train    steps/s of a training run of the same setup fed by that source through the prefetch thread, wall clock, and how
          long the trainer waited for batches.
-`--only stages|source|train`; `--batches N` (default 20)."""
+augin    the input augmentation (`input_augment`): device-event ms per launch and per array (every node
+         applied) at the two shipped input arrays, (6, 24, 148, 148) and (10, 24, 148, 148); then batches/s of the source and
+         steps/s of the fed trainer without the key, with it, and without it again, in this one session.
+`--only stages|source|train|augin`; `--batches N` (default 20)."""
 import argparse, json, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -92,8 +95,8 @@ def stages_part():
     return {"part": "stages", "generated_shape": list(gen), "labels_in_volume": len(ids), "ms": res}
 
 
-def source_part(batches):
-    src = SyntheticSource(NET, VOXEL, 0, seed=42)
+def source_part(batches, input_augment=None):
+    src = SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment)
     next(src)
     torch.cuda.synchronize()
     per = []
@@ -102,30 +105,22 @@ def source_part(batches):
         next(src)
         torch.cuda.synchronize()
         per.append(time.perf_counter() - t)
-    return {"part": "source", "batches": batches, "batches_per_s": batches / sum(per), "ms_median": 1e3 * float(np.median(per)),
+    return {"part": "source", "input_augment": input_augment is not None, "batches": batches, "batches_per_s": batches / sum(per), "ms_median": 1e3 * float(np.median(per)),
             "ms_min": 1e3 * min(per), "ms_max": 1e3 * max(per)}
 
 
-def train_part(batches):
+def make_trainer():
     from bootstrapper_amd.training import Trainer
     from bootstrapper_amd.unet import Model
     model = Model(NET, device=0, precision="f32")
     model.load_state_dict(default_init(NET, seed=42))
     settings = training_settings(NET)
-    trainer = Trainer(model, settings["in_shape"], lr=settings["lr"])
-    res = {"part": "train", "steps": batches}
-    # the trainer alone: one batch fed again and again
-    one = next(SyntheticSource(NET, VOXEL, 0, seed=42))
-    for _ in range(3):
-        trainer.training_step(one)
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    for _ in range(batches):
-        trainer.training_step(one)
-    torch.cuda.synchronize()
-    res["trainer_alone_steps_per_s"] = batches / (time.perf_counter() - t)
-    # fed by the source through the prefetch thread
-    src = PrefetchSource(SyntheticSource(NET, VOXEL, 0, seed=42), 4, 0)
+    return Trainer(model, settings["in_shape"], lr=settings["lr"])
+
+
+def fed(trainer, batches, input_augment=None):
+    """steps/s of `trainer` fed by the source through the prefetch thread, wall clock, and how long it waited for batches"""
+    src = PrefetchSource(SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment), 4, 0)
     try:
         for _ in range(3):
             trainer.training_step(next(src))
@@ -140,17 +135,69 @@ def train_part(batches):
         wall = time.perf_counter() - t
     finally:
         src.close()
+    return {"input_augment": input_augment is not None, "fed_steps_per_s": batches / wall, "waited_for_batches_s": waited, "wall_s": wall}
+
+
+def augin_part(batches):
+    from bootstrapper_amd import augment_inputs as A
+    res = {"part": "augin", "launch_ms": {}, "source": [], "train": []}
+    for shape in ((6,) + SHAPE, (10,) + SHAPE):
+        c, d = shape[:2]
+        x = torch.rand(shape, dtype=torch.float32, device="cuda")
+        rng = np.random.default_rng(1)
+        on = A.InputAugParams(noise_p=1.0, channel_intensity_p=1.0, section_intensity_p=1.0, smooth_p=1.0, blur=(0.5, 1.5), prob_low_contrast=1.0)
+        plan = A.draw_input_plan(rng, on, shape)
+        t = {k: torch.from_numpy(getattr(plan, k)).cuda() for k in ("channel_scale", "channel_shift", "section_scale", "section_shift", "weights",
+                                                                     "radius", "low_contrast")}
+        mc, mz = A.group_mean(x, 0), A.group_mean(x, 1)
+        res["launch_ms"]["x".join(str(v) for v in shape)] = {
+            "noise": events(lambda: A.noise(x, plan.seed, plan.noise_sigma)),
+            "group_mean_channel": events(lambda: A.group_mean(x, 0)),
+            "group_mean_section": events(lambda: A.group_mean(x, 1)),
+            "intensity_channel": events(lambda: A.intensity(x, mc, t["channel_scale"], t["channel_shift"], 0)),
+            "intensity_section": events(lambda: A.intensity(x, mz, t["section_scale"], t["section_shift"], 1)),
+            "smooth": events(lambda: A.smooth(x, t["weights"], t["radius"], True)),
+            "smooth_plane_only": events(lambda: A.smooth(x, t["weights"], t["radius"], False)),
+            "contrast": events(lambda: A.contrast(x, mz, t["low_contrast"], 0.1)),
+            "array_every_node": events(lambda: A.apply_inputs(x, plan)),
+            "voxels": int(x.numel()), "sections_smoothed": int((plan.radius > 0).sum()), "channels": c, "sections": d}
+    params = A.InputAugParams()
+    for key in (None, params, None):     # plain and augmented runs alternating in one session
+        res["source"].append({k: v for k, v in source_part(batches, key).items() if k != "part"})
+    trainer = make_trainer()
+    for key in (None, params, None):
+        res["train"].append(fed(trainer, batches, key))
     trainer.close()
-    res.update(fed_steps_per_s=batches / wall, waited_for_batches_s=waited, wall_s=wall)
+    return res
+
+
+def train_part(batches):
+    trainer = make_trainer()
+    res = {"part": "train", "steps": batches}
+    # the trainer alone: one batch fed again and again
+    one = next(SyntheticSource(NET, VOXEL, 0, seed=42))
+    for _ in range(3):
+        trainer.training_step(one)
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(batches):
+        trainer.training_step(one)
+    torch.cuda.synchronize()
+    res["trainer_alone_steps_per_s"] = batches / (time.perf_counter() - t)
+    # fed by the source through the prefetch thread
+    f = fed(trainer, batches)
+    trainer.close()
+    res.update(fed_steps_per_s=f["fed_steps_per_s"], waited_for_batches_s=f["waited_for_batches_s"], wall_s=f["wall_s"])
     return res
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["stages", "source", "train"])
+    ap.add_argument("--only", choices=["stages", "source", "train", "augin"])
     ap.add_argument("--batches", type=int, default=20)
     a = ap.parse_args()
-    for name, fn in (("stages", stages_part), ("source", lambda: source_part(a.batches)), ("train", lambda: train_part(a.batches))):
+    for name, fn in (("stages", stages_part), ("source", lambda: source_part(a.batches)), ("train", lambda: train_part(a.batches)),
+                     ("augin", lambda: augin_part(a.batches))):
         if a.only in (None, name):
             print(json.dumps(fn()), flush=True)
 

@@ -1,17 +1,16 @@
 """Blosc frames made on the device (csrc/blosc_dev.hip: `bsmi_blosc_encode_dev_u64`, what `bs segment` writes its label volumes
-with) decode -- through this repository's host codec AND through c-blosc itself where the image has it -- to the chunks they
-were made from: label volumes (long runs), noise (planes stored verbatim, whole frames stored), chunks that overhang the array
-(fill 0), strided sources.  Needs an MI355X."""
+with) decode -- through this repository's host codec, through the reader of tests/blosc_ref.py that enforces the Blosc-1 and LZ4
+block formats, AND through c-blosc itself where the image has it -- to the chunks they were made from: label volumes (long runs),
+noise (planes stored verbatim, whole frames stored), chunks that overhang the array (fill 0), strided sources.  Needs an MI355X."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+import blosc_ref
 
-REAL_BLOSC = "/opt/conda/lib/libblosc.so.1"
+pytestmark = pytest.mark.gpu
 
 
 def _encode(vol, chunk, view=None):
@@ -81,12 +80,13 @@ def test_device_frames_decode_to_the_chunks(shape, chunk, kind):
         host.reshape(-1)[-5000:] = 77
     vol = torch.from_numpy(host.view(np.int64)).cuda()
     codec = _lib.Codec(_lib.CODEC_BLOSC, 5, _lib.BLOSC_LZ4, 1, 8, 0)
-    real = C.CDLL(REAL_BLOSC) if os.path.exists(REAL_BLOSC) else None
+    real = blosc_ref.find_c_blosc()
     total = 0
     for g, frame in _encode(vol, chunk):
         want = _expected(host, g, chunk)
         got = codecs.decode(codec, frame, want.nbytes)
         assert got.size == want.nbytes and np.array_equal(got.view(np.uint64).reshape(chunk), want), (kind, g)
+        assert blosc_ref.blosc1_frame_strict(frame)[0] == want.tobytes(), (kind, g)   # ... and nothing in it is off the formats
         if real is not None:     # c-blosc 1.21 reads the same frame
             out = np.empty(want.nbytes, np.uint8)
             n = real.blosc_decompress(frame, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size))

@@ -124,6 +124,109 @@ def rank_blocks(blocks, rank, world):
     return blocks[start:start + q + (1 if rank < r else 0)]
 
 
+DEVICE_FRAME_BLOCK = 32 * 1024      # Blosc block size of the frames csrc/blosc_dev_u8.hip makes
+DEVICE_FRAME_MAX_BLOCKS = 1024
+# `bs predict` makes the Blosc frames of its output chunks on the device only where asked to (BSMI_PRED_DEVICE_FRAMES=1): on the
+# 1024^3 store the command was 0.21 s slower with it (10.14 / 10.19 s against 9.92 / 9.98 s, one rank, 16 host cores) although the
+# writer threads' time fell from 49.6 to 12 s -- they were not on the critical path there.
+PRED_DEVICE_FRAMES_DEFAULT = False
+
+
+def pred_device_frames_enabled(environ=None):
+    """the switches: BSMI_DEVICE_FRAMES=0 turns every device-made frame off (the label volumes' too), BSMI_PRED_DEVICE_FRAMES=0 / 1
+    turns this path alone, without either PRED_DEVICE_FRAMES_DEFAULT holds"""
+    env = os.environ if environ is None else environ
+    if env.get("BSMI_DEVICE_FRAMES", "1") == "0":
+        return False
+    own = env.get("BSMI_PRED_DEVICE_FRAMES")
+    return PRED_DEVICE_FRAMES_DEFAULT if own not in ("0", "1") else own == "1"
+
+
+def pred_device_frames_refusal(ds, blk, hi):
+    """Why the chunks of one output block -- ds[:, blk : blk + hi] -- cannot be made into Blosc frames on the device
+    (csrc/blosc_dev_u8.hip), or None where they can.  Pure: `ds` needs shape, chunks, dtype, codec, fill_value and sep only."""
+    from . import _lib
+    c = ds.codec
+    if c.id != _lib.CODEC_BLOSC or c.cname != _lib.BLOSC_LZ4:
+        return "the compressor is not Blosc lz4"
+    if c.level == 0:
+        return "clevel 0 asks for stored frames"
+    if c.blocksize not in (0, DEVICE_FRAME_BLOCK):
+        return "the compressor sets another block size"
+    if ds.dtype.itemsize != 1:
+        return "items of more than one byte"
+    if ds.fill_value not in (0, None):
+        return "a fill value other than 0"
+    if ds.sep != ".":
+        return "chunk files in nested directories"
+    if len(ds.shape) != 4 or len(ds.chunks) != 4 or ds.chunks[0] != ds.shape[0]:
+        return "the channels are not all in one chunk"
+    if int(np.prod(ds.chunks)) > DEVICE_FRAME_MAX_BLOCKS * DEVICE_FRAME_BLOCK:
+        return "chunks of more than 1024 blocks"
+    if any(b % c_ for b, c_ in zip(blk, ds.chunks[1:])):
+        return "the block starts off the chunk grid"
+    if any(h < 1 or ((b + h) % c_ and b + h != n) for b, h, c_, n in zip(blk, hi, ds.chunks[1:], ds.shape[1:])):
+        return "the block ends off the chunk grid"
+    return None
+
+
+class _DeviceFrames:
+    """The device half of a writer thread of `bs predict`: an output block's chunks are made into Blosc frames where the block
+    lies (two launches per dataset on the thread's I/O stream), the frame sizes and then the frames come to page-locked memory,
+    the files are written from there.  Buffers are kept per thread and grown on demand."""
+
+    def __init__(self, dev):
+        self.dev = dev
+        self.bufs = {}     # thread -> [scratch, frame slots, frame sizes] on the device
+        self.pinned = {}   # thread -> page-locked buffer of the frames
+
+    def write(self, ds, t, blk, hi, st, tid):
+        import ctypes as C
+        import torch
+        from . import _lib
+        cs = [int(v) for v in ds.chunks]
+        grid = [(iz, iy, ix) for iz in range(0, hi[0], cs[1]) for iy in range(0, hi[1], cs[2]) for ix in range(0, hi[2], cs[3])]
+        n = len(grid)
+        origins = (C.c_int64 * (4 * n))(*[v for g in grid for v in (0, *g)])
+        extents = (C.c_int64 * (4 * n))(*[v for g in grid for v in (cs[0], *[min(c_, h - o) for o, c_, h in zip(g, cs[1:], hi)])])
+        slot = (int(_lib.lib.bsmi_blosc_dev_u8_frame_bound(ds.chunk_nbytes)) + 255) // 256 * 256
+        need = int(_lib.lib.bsmi_blosc_dev_u8_scratch_bytes(n, ds.chunk_nbytes))
+        bufs = self.bufs.setdefault(tid, [None, None, None])
+        # Allocated ON the I/O stream: the caching allocator hands a block that was freed on a stream to the next request on the
+        # same stream while the work that used it may still be queued there.  A buffer taken on this thread's current (default)
+        # stream could be the block of a temporary of a forward pass that is still to run -- which would then write into the
+        # encoder's geometry and block starts between its launches.
+        with torch.cuda.stream(st):
+            for k, size in enumerate((need, n * slot, 4 * max(n, 64))):
+                if bufs[k] is None or bufs[k].numel() < size:
+                    bufs[k] = None
+                    bufs[k] = torch.empty(size, dtype=torch.uint8, device=self.dev)
+        scratch, frames, sizes = bufs
+        _lib.check(_lib.lib.bsmi_blosc_encode_dev_u8(self.dev.index, C.c_void_p(t.data_ptr()), (C.c_int64 * 3)(t.stride(0), t.stride(1), t.stride(2)), n,
+                                                      origins, extents, (C.c_int64 * 4)(*cs), C.c_void_p(scratch.data_ptr()), need,
+                                                      C.c_void_p(frames.data_ptr()), slot, C.c_void_p(sizes.data_ptr()), C.c_void_p(st.cuda_stream)))
+        with torch.cuda.stream(st):
+            host_sizes = sizes[:4 * n].view(torch.int32).to("cpu").numpy().astype(np.int64)
+        if (host_sizes < 16).any() or (host_sizes > ds.chunk_nbytes + 16).any():
+            raise RuntimeError(f"{ds.path}: the device encoder reported frame sizes {host_sizes.tolist()}")
+        offs = np.concatenate([[0], np.cumsum(host_sizes)])
+        buf = self.pinned.get(tid)
+        if buf is None or buf.numel() < int(offs[-1]):
+            buf = self.pinned[tid] = torch.empty(max(int(offs[-1]), n * slot // 2), dtype=torch.uint8, pin_memory=True)
+        with torch.cuda.stream(st):
+            for i in range(n):
+                buf[int(offs[i]):int(offs[i + 1])].copy_(frames[i * slot:i * slot + int(host_sizes[i])], non_blocking=True)
+        st.synchronize()
+        host = buf.numpy()
+        os.makedirs(ds.path, exist_ok=True)
+        for i, g in enumerate(grid):
+            path = ds._chunk_path((0, *[(b + o) // c_ for b, o, c_ in zip(blk, g, cs[1:])]))
+            tmp = f"{path}.tmp{os.getpid()}.{tid % 100000}"
+            with open(tmp, "wb") as f:
+                f.write(memoryview(host[int(offs[i]):int(offs[i + 1])]))
+            os.replace(tmp, path)
+
+
 def predict_blocks(cfg, rank=0, world=1, device=None, precision="bf16x3"):
     """Worker body (one per GPU) -> TaskState of its blocks.  precision: bf16x3 (default; within 1e-4 of the reference's
     fp32 forward), f32, or bf16 (throughput mode, 4e-3)."""
@@ -256,27 +359,42 @@ def predict_blocks(cfg, rank=0, world=1, device=None, precision="bf16x3"):
     WRITERS = 8
     pool = cf.ThreadPoolExecutor(max_workers=WRITERS, thread_name_prefix="bsmi-write")
     pinned, copy_streams = {}, {}
+    frames_on, dev_frames = pred_device_frames_enabled(), _DeviceFrames(dev)
 
     def write_block(blk, hi, u8, ready):
         with _trace.span("predict: writer waits for its block", True):
             ready.synchronize()
         # ^ on this pool thread: a copy stream parked behind a device-side wait is a queue the command
         tid = threading.get_ident()   # processor polls for the whole forward pass, at the predict stream's expense
-        if tid not in pinned:
-            pinned[tid] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in u8]
+        if tid not in copy_streams:
             from .volume import io_stream
             copy_streams[tid] = io_stream(dev)
+        # datasets whose chunks can be made into Blosc frames on the device go that way (csrc/blosc_dev_u8.hip), the rest -- other
+        # codecs, blocks off the chunk grid -- through the host as before
+        on_dev = [frames_on and t.dtype == torch.uint8 and t.dim() == 4 and t.stride(3) == 1 and pred_device_frames_refusal(ds, blk, hi) is None
+                  for ds, t in zip(outs, u8)]
+        if any(on_dev):
+            with _trace.span("predict: frames made on the device + files written", True):
+                for ds, t, go in zip(outs, u8, on_dev):
+                    if go:
+                        dev_frames.write(ds, t, blk, hi, copy_streams[tid], tid)
+        if all(on_dev):
+            return
+        if tid not in pinned:
+            pinned[tid] = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in u8]
         host = []
         with torch.cuda.stream(copy_streams[tid]):
-            for buf, t in zip(pinned[tid], u8):
+            for buf, t, go in zip(pinned[tid], u8, on_dev):
                 h = buf[:, :hi[0], :hi[1], :hi[2]]
-                h.copy_(t[:, :hi[0], :hi[1], :hi[2]], non_blocking=True)
+                if not go:
+                    h.copy_(t[:, :hi[0], :hi[1], :hi[2]], non_blocking=True)
                 host.append(h)
         with _trace.span("predict: device -> host copy", True):
             copy_streams[tid].synchronize()
         with _trace.span("predict: encode + write", True):
-            for ds, t in zip(outs, host):
-                ds.write_from((slice(None),) + tuple(slice(blk[d], blk[d] + hi[d]) for d in range(3)), t.numpy())
+            for ds, t, go in zip(outs, host, on_dev):
+                if not go:
+                    ds.write_from((slice(None),) + tuple(slice(blk[d], blk[d] + hi[d]) for d in range(3)), t.numpy())
 
     inflight, redo = [], []
 

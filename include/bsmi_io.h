@@ -111,6 +111,24 @@ int bsmi_blosc_encode_dev_u64(int device, const uint64_t *src_dev, int64_t strid
                               const int64_t *origins, const int64_t *extents, const int64_t chunk_shape[3], void *scratch_dev,
                               size_t scratch_bytes, void *frames_dev, size_t slot_bytes, uint32_t *frame_sizes_dev, void *stream);
 
+/* Blosc frames of a DEVICE-resident array of 1-byte items (the affinity / LSD chunks of `bs predict`), made on the device
+ * (csrc/blosc_dev_u8.hip): Blosc-1, lz4 format, typesize 1, blocks of 32 KiB not split (flags 0x30; the last block may be short,
+ * a frame that would not shrink is stored).  The LZ4 blocks hold matches at offset 1 (runs) and at the distances a 4096-entry
+ * table finds; the rule is written out in blosc_dev_u8.hip and restated in tests/blosc_u8_ref.py, and the frames are byte-equal
+ * to that restatement.  Any Blosc-1 reader decodes them.
+ * src_dev[c * strides[0] + z * strides[1] + y * strides[2] + x] (strides in elements, x contiguous) is the array, chunks are
+ * (C, Z, Y, X) -- a 3-D array has C = 1; chunk i starts at origins[4 i ..] (relative to src_dev), extents[4 i ..] <= chunk_shape
+ * of it exist, the rest of the chunk is fill value 0.  A chunk holds 1 byte ... 1024 blocks (32 MiB); larger ones, null arguments,
+ * extents outside 1 ... chunk_shape, negative origins and slots or scratch below the two bounds give BSMI_ERR_INVALID.
+ * frames_dev: n_chunks slots of slot_bytes >= bsmi_blosc_dev_u8_frame_bound(chunk bytes); frame_sizes_dev[i] = bytes of frame i;
+ * scratch_dev: bsmi_blosc_dev_u8_scratch_bytes(n_chunks, chunk bytes).  Asynchronous on `stream`.  origins, extents, strides and
+ * chunk_shape are read before the call returns (they travel in launch arguments): the caller may free them at once. */
+size_t bsmi_blosc_dev_u8_frame_bound(size_t chunk_bytes);
+size_t bsmi_blosc_dev_u8_scratch_bytes(int n_chunks, size_t chunk_bytes);
+int bsmi_blosc_encode_dev_u8(int device, const uint8_t *src_dev, const int64_t strides[3], int n_chunks, const int64_t *origins,
+                             const int64_t *extents, const int64_t chunk_shape[4], void *scratch_dev, size_t scratch_bytes,
+                             void *frames_dev, size_t slot_bytes, uint32_t *frame_sizes_dev, void *stream);
+
 /* The region adjacency graph of a segmented volume as an SQLite file (the `db` table of the reference's segment config,
  * post/watershed.py:100-117; nodes as post/blockwise/watershed_frags.py:230-246 writes them, edges with their merge scores
  * as waterz_agglom.py:165-170): tables nodes(id PRIMARY KEY, z, y, x, size) and edges(u, v, merge_score, PRIMARY KEY (u, v)),

@@ -63,6 +63,7 @@ STEP_TYPES = ("input", "conv", "pool", "up", "head")
 CONV_FORMS = ("gather", "raster-halo", "box-halo", "halo-resident", "first-pass", "winograd F(2x2)", "winograd F(4x4)")
 STEP_FLAGS = {1: "fused-up", 2: "res-low", 4: "split-k"}
 STEP_BELOW_UP = 8  # reported as plan_steps()'s own key `below_up`, not among the flags
+STEP_WINO_Z = 16   # ... and `wino_z`: the F(4x4) stage is F(2,3) along z as well (csrc/unet_rules.hip wino_z_site)
 
 
 class Codec(C.Structure):
@@ -134,6 +135,8 @@ def _load():
         "bsmi_unet_forward": (i32, [p, i32, vp, i32, i64p, C.POINTER(vp), C.POINTER(vp), vp]),
         "bsmi_unet_debug_activation": (i32, [p, i32, i32, i64p, vp, C.c_uint64]),
         "bsmi_unet_debug_step_info": (i32, [p, i32, C.POINTER(StepInfo), C.POINTER(i32)]),
+        "bsmi_debug_wino_pack_host": (i32, [vp, i32, i32, i32, vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                            C.POINTER(i32), C.POINTER(i32)]),
         "bsmi_unet_profile_enable": (i32, [p, i32]),
         "bsmi_unet_profile_read": (i32, [p, i32, C.POINTER(i32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                          C.POINTER(C.c_double)]),

@@ -6,6 +6,30 @@
 
 extern "C" {
 
+int bsmi_debug_wino_pack_host(const float* w, int cout, int cin, int wz, uint16_t* out, uint64_t capacity, uint64_t* image_elems, uint64_t* batch_elems,
+                              int* npad, int* ksteps) {
+  if (!w || cout < 1 || cin < 1) BSMI_FAIL(BSMI_ERR_INVALID, "bad argument");
+  std::vector<int> cin_of_v;
+  for (int c = 0; c < round_up(cin, kChanPad); ++c) cin_of_v.push_back(c < cin ? c : -1);
+  const int Npad = round_up(cout, tile_bn(choose_tile(cout)));
+  std::vector<WinoUnit> units;
+  wino_units((int)cin_of_v.size(), units, wz ? 1 : 3);
+  if (image_elems || batch_elems || out) {
+    std::vector<uint16_t> packed;
+    size_t ie = 0, be = 0;
+    wino_pack_weights(w, cout, cin, cin_of_v, Npad, units, packed, ie, be, 4, wz != 0);
+    if (image_elems) *image_elems = ie;
+    if (batch_elems) *batch_elems = be;
+    if (out) {
+      if (capacity < packed.size()) BSMI_FAIL(BSMI_ERR_INVALID, "buffer of %llu values too small", (unsigned long long)capacity);
+      memcpy(out, packed.data(), packed.size() * sizeof(uint16_t));
+    }
+  }
+  if (npad) *npad = Npad;
+  if (ksteps) *ksteps = (int)(units.size() / kUnitsPerStep);
+  return BSMI_OK;
+}
+
 int bsmi_unet_debug_activation(bsmi_unet* h, int step, int what, int64_t shape_out[4], float* host_out, uint64_t capacity) {
   if (!h || !shape_out) BSMI_FAIL(BSMI_ERR_INVALID, "null argument");
   Plan* plan = h->last_plan;
@@ -83,6 +107,7 @@ int bsmi_unet_debug_step_info(bsmi_unet* h, int step, bsmi_unet_step_info* info,
       if (up || st.wino_out.low || st.wino_has_below) info->flags |= BSMI_STEP_FUSED_UP;
       if (st.wino_has_below) info->flags |= BSMI_STEP_BELOW_UP;
       if (st.wino_has_res_low) info->flags |= BSMI_STEP_RES_LOW;
+      if (st.wino_in.wz) info->flags |= BSMI_STEP_WINO_Z;
       if (conv_igemm_split_k(st.wino_gemm, plan->prec, st.tile, sk_grid) ||
           (st.wino_has_res && conv_igemm_split_k(st.wino_res, plan->prec, st.tile, sk_grid)) ||
           (st.wino_has_res_low && conv_igemm_split_k(st.wino_res_low, plan->prec, st.tile, sk_grid)) ||

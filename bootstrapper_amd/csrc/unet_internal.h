@@ -72,6 +72,8 @@ struct PackedWino {
   // packed only for the fused upsampling (pack_wino: the narrow last stage of a decoder pass): plan_wino takes this form when
   // the pass runs behind a fused upsampling and leaves the stage to its other forms otherwise
   bool fused_only = false;
+  // F(2,3) along z as well (unet_rules.hip wino_z_site): `units` lists channels only, `w` holds 144 batches (36 e + b)
+  bool wz = false;
   std::vector<WinoUnit> units;      // K-step list of every batch
   std::vector<int> cin_of_v;        // V channel -> input channel of the concatenated input (-1: pad)
   int Cv = 0;                       // channels of V: every source padded to kChanPad
@@ -278,6 +280,7 @@ bool wino_eligible(const PassSite& p, int ci);
 int wino_tile_edge();
 bool wino_narrow_last(const bsmi_unet* h, const PassSite& p, int ci);
 bool below_up_site(const bsmi_unet* h, const PassSite& p, int ci);
+bool wino_z_site(const bsmi_unet* h, const PassSite& p, int ci);
 bool fuse_up_enabled();
 bool pool_fuse_enabled();
 int h16_mode();

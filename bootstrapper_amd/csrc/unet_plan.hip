@@ -518,7 +518,7 @@ int Planner::rec(int level, const TDesc& f_in, TDesc& f_out) {
     // still written, the skip connection reads it.
     PlanStep& prod = plan->steps.back();
     if (pool_fuse_enabled() && prec == BSMI_PREC_BF16X3 && f[0] == 1 && f[1] == 2 && f[2] == 2 && prod.type == PlanStep::CONV && prod.use_wino &&
-        prod.wino_out.m == 4 && !prod.wino_out.low && prod.wino_out.out == f_left.ptr && !(f_left.H & 1) && !(f_left.W & 1)) {
+        prod.wino_out.m == 4 && !prod.wino_out.low && !prod.wino_out.wz && prod.wino_out.out == f_left.ptr && !(f_left.H & 1) && !(f_left.W & 1)) {
       prod.wino_out.pool = g_in.ptr;
       st.pool_fused = true;
     }

@@ -37,6 +37,7 @@ struct WinoStage {
   PlanStep& st;
   bool below;  // the upsampled source leaves the Winograd form (PackedWino::below_*); V holds the skip connection alone
   bool cut;    // the residual branch in two parts: the skip connection here, the upsampled map below the upsampling
+  bool wz;     // F(2,3) along z as well (PackedWino::wz): Dv = pairs of output planes, the GEMM a 1x1x1 convolution of V[36 e + b]
   int wm, nbatch, Dv, Ty, Tx, Cv;
   size_t vbatch, Mrows;  // bytes of one batch of V, rows of one batch of the GEMM
   void *V = nullptr, *Mbuf = nullptr, *addend = nullptr, *low = nullptr, *Ybuf = nullptr;
@@ -68,10 +69,13 @@ struct WinoStage {
     wi.V = V;
     wi.Dv = Dv; wi.Ty = Ty; wi.Tx = Tx; wi.Cv = Cv;
     wi.m = wm;
+    wi.wz = wz ? 1 : 0;
+    wi.Dz = o.D + 2;
     return BSMI_OK;
   }
 
-  // the batched GEMMs: a (3,1,1) convolution of V[b] with U[b]
+  // the batched GEMMs: a (3,1,1) convolution of V[b] with U[b]; wz: a 1x1x1 convolution of V[36 e + b] over the pairs (its
+  // units carry kz = 0: the K-step list is channels only)
   int batched_gemm() {
     const std::vector<WinoUnit>& units = below ? pw.skip_units : pw.units;
     ConvArgs& g = st.wino_gemm;
@@ -92,7 +96,7 @@ struct WinoStage {
     raw_gemm(g, below ? pw.skip_w : pw.w, below ? pw.skip_lo_image_bytes : pw.lo_image_bytes, pw.Npad);
     g.bias = pc.bias;
     g.out = Mbuf;
-    g.Do = o.D; g.Ho = Ty; g.Wo = Tx; g.Co = o.Cpad;
+    g.Do = wz ? Dv : o.D; g.Ho = Ty; g.Wo = Tx; g.Co = o.Cpad;
     g.M = (int)Mrows;
     g.nbatch = nbatch;
     g.a_batch = (int64_t)vbatch;
@@ -237,6 +241,8 @@ struct WinoStage {
     wo.Do = o.D; wo.Ty = Ty; wo.Tx = Tx; wo.Co = o.Cpad;
     wo.m = wm; wo.Ho = o.H; wo.Wo = o.W;
     wo.relu = 1;
+    wo.wz = wz ? 1 : 0;
+    // (nbatch, Mrows and the K-step count are the form's own: 144 batches of ceil(Do / 2) Ty Tx rows over K = Cv in the wz form)
     const double kstep = (double)kUnitsPerStep * sube(prec);
     st.exec_flops = 2.0 * (double)round_up((int)Mrows, 256) * pw.Npad * ((double)st.wino_gemm.nsteps * kstep) * nbatch * 3.0;
     if (st.wino_has_res) st.exec_flops += 2.0 * (double)round_up(st.wino_res.M, 256) * pw.Npad * ((double)st.wino_res.nsteps * kstep) * 3.0;
@@ -256,26 +262,29 @@ int Planner::plan_wino(PassSite& p, int ci, const PackedConv& pc, const TDesc* s
   const PackedWino& pw = p.wino[ci];
   const bool wants_fused = fuse_up && (ci == 0 || ci == p.nconv - 1);
   if (pw.fused_only && !fuse_up) return BSMI_OK;  // the upsampling of this pass is not fused: the stage keeps its other form
-  const int wm = pw.m, nbatch = wino_batches(wm);
+  const bool wz = pw.wz;
+  const int wm = pw.m, nbatch = wino_batches(wm) * (wz ? kWinoZ : 1);
+  if (wz && (wm != 4 || wants_fused)) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: packed for the z transform, but planned behind a fused upsampling", p.prefix.c_str(), ci);
   if (prec != BSMI_PREC_BF16X3 || !pw.ready || (wm == 2 && ((o.H & 1) || (o.W & 1))) || st.use_box || st.use_rh) {
     if (wants_fused) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: the upsampling was fused into this stage, which cannot take the Winograd form", p.prefix.c_str(), ci);
     return BSMI_OK;
   }
   // below-up: the upsampled source leaves the Winograd form (PackedWino::below_*); V holds the skip connection alone
   const bool below = fuse_up && ci == 0 && pw.below_ready && wm == 4 && nsl == 2;
-  const int Dv = o.D + 2, Ty = (o.H + wm - 1) / wm, Tx = (o.W + wm - 1) / wm, Cv = below ? pw.skip_Cv : pw.Cv;   // F(4x4): the last tiles may overhang
+  const int Dv = wz ? (o.D + 1) / 2 : o.D + 2, Ty = (o.H + wm - 1) / wm, Tx = (o.W + wm - 1) / wm, Cv = below ? pw.skip_Cv : pw.Cv;   // F(4x4): the last tiles may overhang
   const size_t vbatch = (size_t)Dv * Ty * Tx * Cv * 4;  // bytes of one batch of V: (hi, lo) pairs
   if (vbatch >= ((size_t)1 << 31)) {                     // 31-bit byte offsets inside a batch
     if (wants_fused) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: fused upsampling, but the transformed input is too large", p.prefix.c_str(), ci);
     return BSMI_OK;
   }
-  const size_t Mrows = (size_t)o.D * Ty * Tx;
+  const size_t Mrows = (size_t)(wz ? Dv : o.D) * Ty * Tx;
+  if (Mrows >= ((size_t)1 << 31)) BSMI_FAIL(BSMI_ERR_STATE, "%s conv %d: too many rows in a batch of the transform-domain GEMM", p.prefix.c_str(), ci);
   // residual branch
   const bool cut = fuse_up && ci == p.nconv - 1;  // the branch in two parts: the skip connection here, the upsampled map below the upsampling
-  WinoStage w{plan, fuse_up, p, ci, pc, pw, slots, so, o, st, below, cut, wm, nbatch, Dv, Ty, Tx, Cv, vbatch, Mrows};
-  BSMI_HIP(hipMalloc(&w.V, nbatch * vbatch + 4096));
+  WinoStage w{plan, fuse_up, p, ci, pc, pw, slots, so, o, st, below, cut, wz, wm, nbatch, Dv, Ty, Tx, Cv, vbatch, Mrows};
+  BSMI_HIP(hipMalloc(&w.V, (size_t)nbatch * vbatch + 4096));
   plan->allocs.push_back(w.V);
-  BSMI_HIP(hipMalloc(&w.Mbuf, nbatch * Mrows * o.Cpad * sizeof(float)));
+  BSMI_HIP(hipMalloc(&w.Mbuf, (size_t)nbatch * Mrows * o.Cpad * sizeof(float)));
   plan->allocs.push_back(w.Mbuf);
   plan->bytes += nbatch * (vbatch + Mrows * o.Cpad * sizeof(float));
   int rc = w.input_transform();

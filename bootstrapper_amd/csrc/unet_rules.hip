@@ -109,6 +109,48 @@ bool pool_fuse_enabled() {
   return pool_fuse;
 }
 
+// Which F(4x4) stages take the "wz" form, F(2,3) along z as well (wino.h WinoInArgs::wz): 144 batches of
+// K = Cin over pairs of output planes instead of 36 of K = 3 Cin over planes, two thirds of the multiplies, V and M twice the
+// size.  BSMI_WINO_Z, read once per process: 0 = none, 1 = every stage the kernels can take (tests), unset = the rule.
+// The kernels take a stage whose transforms carry nothing else: no source read through a fused upsampling and no sums from
+// below it (the first and the last stage of a decoder pass behind a (1,2,2) upsampling), no pooled output (the last stage of
+// an encoder pass before a (1,2,2) pooling) -- those keep the plain F(4x4) form, decided here from the site alone so that one
+// set of weight images is packed.
+static int wino_z_mode() {
+  static const int m = [] { const char* e = getenv("BSMI_WINO_Z"); return e ? atoi(e) : -1; }();
+  return m;
+}
+bool wino_z_site(const bsmi_unet* h, const PassSite& p, int ci) {
+  if (wino_z_mode() == 0 || wino_tile_edge() != 4 || !wino_eligible(p, ci)) return false;
+  int cin = p.cout;
+  if (ci == 0) {
+    cin = 0;
+    for (int s = 0; s < p.nslots; ++s) cin += p.cin[s];
+  }
+  if (&p >= h->r_conv.data() && &p < h->r_conv.data() + h->r_conv.size()) {
+    const int* f = h->cfg.downsample_factors[&p - h->r_conv.data()];
+    const bool fusable = fuse_up_enabled() && p.nslots == 2 && f[0] == 1 && f[1] == 2 && f[2] == 2;   // what Planner::rec can fuse
+    if (fusable && (ci == 0 || ci == p.nconv - 1)) return false;
+  } else if (&p >= h->l_conv.data() && &p < h->l_conv.data() + h->l_conv.size()) {
+    const size_t i = &p - h->l_conv.data();
+    if (i + 1 < h->l_conv.size() && ci == p.nconv - 1) {   // a pooling follows
+      const int* f = h->cfg.downsample_factors[i];
+      if (pool_fuse_enabled() && f[0] == 1 && f[1] == 2 && f[2] == 2) return false;
+    }
+  } else {
+    return false;
+  }
+  if (wino_z_mode() >= 1) return true;
+  // The rule: the stages measured to gain more than the spread of three repeats of tools/probe_unet.py bf16x3 on the 128^3
+  // block (ms per launch, min-max, BSMI_WINO_Z=0 -> 1): 1500 -> 1500 4.09-4.20 -> 3.80-3.88 gains;
+  // 300 -> 1500 1.48-1.51 -> 1.73-1.74 and 60 -> 300 0.77-0.78 -> 1.28-1.29 lose.  Both 300 -> 300 stages of that block cannot take
+  // the form (one stores the pooled output, the other is the last stage of a fused decoder pass: 1.79-1.81 and 1.22-1.24 either
+  // way), nor can 1800 -> 300.  A batch of the wz GEMM gives the matrix pipe 6 R Cin Npad FLOP for 4 R (Cin + Npad) bytes of V and
+  // M: 1140 FLOP/B for 1504 -> 1536, 381 and 80 for the two losers against the chip's balance of about 500 -- below it the doubled
+  // V and M cost more than the multiplies return.  Hence both sides at least 1024 channels.
+  return cin >= 1024 && p.cout >= 1024;
+}
+
 // Which stages run in the halo-resident form (conv_h16.hip).  BSMI_H16: 0 = none, unset / 1 = the stages with at most 64 output
 // channels whose launch is large enough to fill the chip, 2 = every stage the kernel can take (tests: small nets).
 int h16_mode() {

@@ -8,8 +8,9 @@
 namespace bsmi {
 
 constexpr int kWinoBatch = 16;  // F(2x2): transform positions (xi, nu) of a 4 x 4 input tile, b = 4 * xi + nu
-constexpr int kWinoMaxBatch = 36;  // F(4x4): 6 x 6 input tile, b = 6 * xi + nu
+constexpr int kWinoMaxBatch = 144;  // F(4x4): 6 x 6 input tile, b = 6 * xi + nu; its "wz" form: 4 z positions e of each, batch 36 e + b
 inline int wino_batches(int m) { return (m + 2) * (m + 2); }
+constexpr int kWinoZ = 4;  // the wz form: z positions e of a pair of output planes (F(2,3) along z, see WinoInArgs::wz)
 constexpr int kWinoMaxSrc = 2;  // source tensors of the input transform (skip connection + upsampled map)
 
 // Input transform: V[b][z][ty][tx][c] = (B^T d B)[xi][nu] of the 4 x 4 in-plane tile d whose first voxel is
@@ -30,6 +31,13 @@ struct WinoInArgs {
   int m;    // 2 (0 reads as 2) or 4: tile (ty, tx) starts at voxel (m ty, m tx); F(4x4) tiles may overhang the layer's input (the
             // last tile row / column of an extent that is no multiple of 4): reads are clamped to the source, the outputs
             // that depend on them are never stored
+  // wz = 1 (m = 4 only, no upsampled source): F(4x4) in (y, x) (x) F(2,3) along z.  V[e][b][r][ty][tx][c], Dv = ceil(Do / 2) pairs
+  // r of output planes: position e of pair r is the in-plane transform of ONE combination of two input planes, with
+  // B^T_z = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1] over the planes 2r .. 2r + 3 of the layer's input:
+  //   e = 0: d[2r] - d[2r+2]    e = 1: d[2r+1] + d[2r+2]    e = 2: d[2r+2] - d[2r+1]    e = 3: d[2r+1] - d[2r+3]
+  // Dz = planes of the layer's input (Do + 2): the last pair of an odd Do overhangs by one plane, whose reads are clamped to
+  // plane Dz - 1 like the rows and columns of an overhanging tile (it only reaches the output plane that is never stored)
+  int wz, Dz;
 };
 
 // Output transform: out[z][2 ty + p][2 tx + q][c] = relu( (A^T M A)[p][q] + bias[c] + addend[...] ) as (hi, lo) pairs, where
@@ -60,6 +68,10 @@ struct WinoOutArgs {
   // holds.  The maximum is taken over the values as stored (hi + lo), as unet_ops.hip maxpool_kernel takes it over what it
   // reads back: the same bits.  `out` is still written whole
   void* pool;
+  // wz = 1 (m = 4, no low / below / pool): M is [4][36][ceil(Do / 2) * Ty * Tx][Co] (WinoInArgs::wz); per position e the in-plane
+  // transform t_e = A^T M_e A, then A^T_z = [1 1 1 0; 0 1 -1 -1] in this order: out[2r] = (t0 + t1) + t2, out[2r + 1] = (t1 - t2) - t3
+  // (not stored when 2r + 1 = Do); bias, addend, ReLU and the (hi, lo) split after that, as in the plain form
+  int wz;
 };
 
 int launch_wino_in(const WinoInArgs& a, hipStream_t s);
@@ -70,18 +82,22 @@ struct WinoUnit {
   int kz, vc0;
   bool dummy;
 };
-// K-step list shared by the 16 batches: 32-channel chunks of V, the three z taps inside a chunk; even number of K-steps.
-void wino_units(int Cv, std::vector<WinoUnit>& out);
+// K-step list shared by the batches: 32-channel chunks of V, the `taps` z taps inside a chunk (3; the wz form, whose z taps
+// are part of the transform: 1, channels only, every kz = 0); even number of K-steps.
+void wino_units(int Cv, std::vector<WinoUnit>& out, int taps = 3);
 
 // Host side: transformed weights U[b][kz][c][n] = sum_{ky,kx} G[xi][ky] G[nu][kx] w[n][cin(c)][kz][ky][kx], packed as the GEMM's
 // B operand [b][K-step][Npad][64 B], hi image then lo image (each `image_elems` bf16 values, slack rows included).
 // `cin_of_v[c]`: input channel of V channel c, or -1 for a pad channel.  `w`: OIDHW f32 with `cin` input channels.
 void wino_pack_weights(const float* w, int cout, int cin, const std::vector<int>& cin_of_v, int Npad, const std::vector<WinoUnit>& units,
-                       std::vector<uint16_t>& packed, size_t& image_elems, size_t& batch_elems, int m = 2);
+                       std::vector<uint16_t>& packed, size_t& image_elems, size_t& batch_elems, int m = 2, bool wz = false);
+// wz (m = 4, `units` with one tap): the z taps are transformed too, G_z = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]:
+//   U[e][b][c][n] = G_z[e][0] u_0 + G_z[e][1] u_1 + G_z[e][2] u_2,   u_kz = (G g_kz G^T)[b] before its rounding,
+// in double and in this order, rounded to f32 once, then split; 144 batches, batch 36 e + b.
 
 // The same images made on the device from the stage's raw weights (uploaded for the call): *image_dev = hi image then lo image
 // (hipMalloc'ed, the caller frees it); bit for bit what wino_pack_weights makes.
 int wino_pack_weights_dev(const float* w, int cout, int cin, const std::vector<int>& cin_of_v, int Npad, const std::vector<WinoUnit>& units, int m,
-                          void** image_dev, size_t& image_elems, size_t& batch_elems);
+                          void** image_dev, size_t& image_elems, size_t& batch_elems, bool wz = false);
 
 }  // namespace bsmi

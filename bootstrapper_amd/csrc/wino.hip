@@ -10,6 +10,7 @@
 // implicit-GEMM kernel (conv_igemm.hip, ConvArgs::nbatch) with raw f32 sums as its output.  This file holds the two
 // memory-bound transforms around it and the host-side weight transform.  F(2x2):
 //   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1]   G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]   A^T = [1 1 1 0; 0 1 -1 -1]
+// The widest stage is F(2,3) along z as well (the "wz" form, WinoInArgs::wz: 144 batches of K = Cin over pairs of output planes).
 // Arithmetic: d = hi + lo is exact in f32; B^T d B is sums of four such values (f32 rounding, 2^-24); V and U are stored as
 // (hi, lo) bf16 pairs like every operand of this mode (2^-17 per product); M and A^T M A are f32.  Measured against the direct
 // form on the full-size block: DESIGN.md section 4.
@@ -446,7 +447,16 @@ __device__ __forceinline__ void store_split4_pair(uint16_t* p, int hf, const flo
 // never stored.  The 36 planes of V are walked with ONE running pointer: as 36 offsets from the tile's element they were
 // hoisted out of the tile loop, 72 registers that kept the kernel at 256 + 12 registers and one wave per SIMD (now 202 and
 // two, which the launch bounds ask for: one wave per SIMD is 20 % slower at S = 1).
-__global__ __launch_bounds__(256, 2) void wino4_in_kernel(const WinoInArgs a, int src, size_t total, int S, int nseg) {
+// WZ (WinoInArgs::wz): the thread takes position e of z-pair r.  Its 6 x 6 patch is the element-wise combination of the same
+// patch of TWO input planes, pa + sgn pb in f32 as the values are loaded (one rounding, 2^-24), and everything after that is
+// the unchanged in-plane transform into batch 36 e + b: the live set stays at 144 values.  Thread order: channel group, segment,
+// e, tile row, pair -- the four positions of a pair, which read the same four planes, sit in neighbouring workgroups of one XCD
+// and meet in its L2.  The second plane is one element offset from the first, not six more row addresses.
+// One wave per SIMD for WZ: with twice the loads of a column in flight the kernel wants 24 bytes more than 256 registers hold,
+// in every arrangement of its addresses that was tried (a base pointer per plane, 32-bit offsets made per load, loads fenced
+// in groups: 200 bytes and more); what the lower occupancy costs is part of the stage's measured time.
+template <bool WZ = false>
+__global__ __launch_bounds__(256, WZ ? 1 : 2) void wino4_in_kernel(const WinoInArgs a, int src, size_t total, int S, int nseg) {
   const unsigned nb = gridDim.x, q = nb >> 3, r = nb & 7, xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const unsigned blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
   const size_t i = (size_t)blk * blockDim.x + threadIdx.x;
@@ -456,26 +466,50 @@ __global__ __launch_bounds__(256, 2) void wino4_in_kernel(const WinoInArgs a, in
   size_t t = i / ncg;
   const int tx0 = (int)(t % nseg) * S, tx1 = tx0 + S < a.Tx ? tx0 + S : a.Tx;
   t /= nseg;
+  int ze = 0;
+  if constexpr (WZ) {
+    ze = (int)(t & 3);
+    t >>= 2;
+  }
   const int ty = (int)(t % a.Ty);
-  const int z = (int)(t / a.Ty);
+  const int z = (int)(t / a.Ty);   // WZ: the pair r
   const uint16_t* sp = (const uint16_t*)a.src[src];
   const int H = a.H[src], W = a.W[src], C = a.Cpad[src];
+  // WZ: planes (za, zb) of the layer's input and the sign of the second: (2r, 2r+2, -), (2r+1, 2r+2, +), (2r+2, 2r+1, -), (2r+1, 2r+3, -)
+  int za = z, zb = z;
+  [[maybe_unused]] float sgn = -1.f;
+  if constexpr (WZ) {
+    za = 2 * z + (ze == 0 ? 0 : ze == 2 ? 2 : 1);
+    zb = 2 * z + (ze == 2 ? 1 : ze == 3 ? 3 : 2);
+    za = za < a.Dz - 1 ? za : a.Dz - 1;
+    zb = zb < a.Dz - 1 ? zb : a.Dz - 1;
+    sgn = ze == 1 ? 1.f : -1.f;
+  }
   size_t erow[6];
 #pragma unroll
   for (int rr = 0; rr < 6; ++rr) {
     int y = 4 * ty + a.oy[src] + rr;
     y = y < H - 1 ? y : H - 1;
-    erow[rr] = (((size_t)(z + a.oz[src]) * H + y) * W) * C + 8 * cv;
+    erow[rr] = (((size_t)(za + a.oz[src]) * H + y) * W) * C + 8 * cv;
   }
+  [[maybe_unused]] const ptrdiff_t eb = (ptrdiff_t)(zb - za) * ((ptrdiff_t)H * W * C);  // WZ: from plane za to plane zb, elements
   const size_t plane = (size_t)a.Dv * a.Ty * a.Tx * a.Cv;
-  const size_t e_out = (((size_t)z * a.Ty + ty) * a.Tx) * a.Cv + a.cv0[src] + 8 * cv;
+  const size_t e_out = (((size_t)z * a.Ty + ty) * a.Tx) * a.Cv + a.cv0[src] + 8 * cv + (WZ ? (size_t)ze * 36 * plane : 0);
   float col[6][6][4];  // col[c][xi]: (B^T d)[xi] of input column 4 tx + c
   auto load_col = [&](int c, int x) __attribute__((always_inline)) {
     x += a.ox[src];
     x = x < W - 1 ? x : W - 1;
     float d[6][4];
 #pragma unroll
-    for (int rr = 0; rr < 6; ++rr) load_split4(sp, erow[rr] + (size_t)x * C, hf, d[rr]);
+    for (int rr = 0; rr < 6; ++rr) {
+      load_split4(sp, erow[rr] + (size_t)x * C, hf, d[rr]);
+      if constexpr (WZ) {
+        float d2[4];
+        load_split4(sp, (size_t)((ptrdiff_t)(erow[rr] + (size_t)x * C) + eb), hf, d2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[rr][k] += sgn * d2[k];
+      }
+    }
     bt4_apply(d, col[c]);
   };
   load_col(0, 4 * tx0);
@@ -787,6 +821,106 @@ __global__ __launch_bounds__(256) void wino4_out_kernel(const WinoOutArgs a, siz
   }
 }
 
+// The output transform of the wz form (WinoOutArgs::wz): one thread, 4 channels of the 4 x 4 tile (ty, tx) of BOTH output planes
+// of z-pair r.  Per position e every M element is read once: A^T goes over each column as its six values arrive (4 x 6
+// intermediates), then over the rows, t_e = A^T M_e A; t_e is folded at once into the two running planes in the fixed order
+//   out[2r] = (t0 + t1) + t2,   out[2r + 1] = (t1 - t2) - t3,
+// so what is live is one position's intermediates and two planes of 16 sums.  Bias, addend, ReLU and the split follow as in
+// wino4_out_kernel; rows, columns and the second plane past the output's extent are not stored.
+__global__ __launch_bounds__(256) void wino4z_out_kernel(const WinoOutArgs a, size_t total) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int ncg = a.Co >> 2;
+  const int cg = (int)(i % ncg), cv = cg >> 1, hf = cg & 1;
+  size_t t = i / ncg;
+  const int tx = (int)(t % a.Tx);
+  t /= a.Tx;
+  const int ty = (int)(t % a.Ty);
+  const int r = (int)(t / a.Ty);
+  const size_t Mrows = (size_t)((a.Do + 1) >> 1) * a.Ty * a.Tx;
+  const size_t m = ((size_t)r * a.Ty + ty) * a.Tx + tx;
+  const float* mp = a.M + m * a.Co + 4 * cg;      // batch 36 e of this tile: moves on by 36 batches per position
+  const size_t bstride = Mrows * a.Co;
+  float o0[4][4][4], o1[4][4][4];  // [p][q][channel] of planes 2r and 2r + 1
+#pragma unroll
+  for (int e = 0; e < kWinoZ; ++e) {
+    float tp[6][4][4];  // tp[nu][p]: (A^T M_e)[p][nu]
+#pragma unroll
+    for (int nu = 0; nu < 6; ++nu) {
+      float mm[6][4];
+#pragma unroll
+      for (int xi = 0; xi < 6; ++xi) {
+        const f32x4_t v = __builtin_nontemporal_load((const f32x4_t*)(mp + (size_t)(6 * xi + nu) * bstride));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mm[xi][k] = v[k];
+      }
+      at4_apply(mm, tp[nu]);
+    }
+    mp += 36 * bstride;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      float in[6][4], y[4][4];   // row p of A^T M_e, then A^T over it: y[q] = t_e[p][q]
+#pragma unroll
+      for (int nu = 0; nu < 6; ++nu)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) in[nu][k] = tp[nu][p][k];
+      at4_apply(in, y);
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (e == 0) o0[p][q][k] = y[q][k];
+          if (e == 1) { o0[p][q][k] += y[q][k]; o1[p][q][k] = y[q][k]; }
+          if (e == 2) { o0[p][q][k] += y[q][k]; o1[p][q][k] -= y[q][k]; }
+          if (e == 3) o1[p][q][k] -= y[q][k];
+        }
+    }
+    // one position's 36 loads in flight at a time: its sums are pinned before the loads of the next (left to itself the
+    // compiler issued all 144 first: 502 + 246 registers, one wave per SIMD)
+    if (e < kWinoZ - 1) {
+#pragma unroll
+      for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) asm volatile("" : "+v"(o0[p][q][k]) : : "memory");
+    }
+  }
+  float bv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) bv[k] = a.bias[4 * cg + k];
+  uint16_t* out = (uint16_t*)a.out;
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    const int z = 2 * r + pl;
+    if (z >= a.Do) continue;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      const int oy = 4 * ty + p;
+      if (oy >= a.Ho) continue;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int ox = 4 * tx + q;
+        if (ox >= a.Wo) continue;
+        const size_t e8 = (((size_t)z * a.Ho + oy) * a.Wo + ox) * a.Co + 8 * cv;
+        float v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (pl ? o1[p][q][k] : o0[p][q][k]) + bv[k];
+        if (a.addend) {
+          const f32x4_t r0 = __builtin_nontemporal_load((const f32x4_t*)(a.addend + e8 + 4 * hf));
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] += r0[k];
+        }
+        if (a.relu) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.f;
+        }
+        store_split4(out, e8, hf, v);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // How the F(4x4) input transforms cut a row of Tx tiles into segments (one thread: 4 channels of one segment).
@@ -811,6 +945,8 @@ int launch_wino_in(const WinoInArgs& a, hipStream_t s) {
   const int m = a.m == 4 ? 4 : 2;
   if (a.m != 0 && a.m != 2 && a.m != 4) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: tile edge %d (2 or 4)", a.m);
   if (a.nsrc < 1 || a.nsrc > kWinoMaxSrc || a.Dv <= 0 || a.Ty <= 0 || a.Tx <= 0 || a.Cv % 8) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: bad geometry");
+  // the wz form: F(4x4) tiles, Dv pairs of output planes over Dz = Do + 2 input planes, Do = 2 Dv or 2 Dv - 1
+  if (a.wz && (m != 4 || a.Dz < 3 || (a.Dz - 2 + 1) / 2 != a.Dv)) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: bad geometry of the z transform");
   for (int q = 0; q < a.nsrc; ++q) {
     if (a.Cpad[q] % 8 || a.cv0[q] % 8 || a.cv0[q] + a.Cpad[q] > a.Cv) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: bad channel layout of source %d", q);
     const int upf = a.upf[q] > 0 ? a.upf[q] : 1;  // an upsampled source is upf times as large in the plane
@@ -821,9 +957,10 @@ int launch_wino_in(const WinoInArgs& a, hipStream_t s) {
     int S = a.Tx, nseg = 1;
     if (m == 4) wino_in_segments(a.Tx, S, nseg);
     // one thread per (z, tile row, 8 channels); F(4x4): per (z, tile row, segment of the row, 4 channels)
-    const size_t total = (size_t)a.Dv * a.Ty * (a.Cpad[q] / (m == 4 ? 4 : 8)) * nseg;
+    const size_t total = (size_t)a.Dv * a.Ty * (a.Cpad[q] / (m == 4 ? 4 : 8)) * nseg * (a.wz ? kWinoZ : 1);
     const dim3 grid((unsigned)((total + 255) / 256));
     if (a.upf[q] > 0) {
+      if (a.wz) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: the z transform does not read through an upsampling");
       if (a.upf[q] != 2 || a.oy[q] < 0 || a.ox[q] < 0) BSMI_FAIL(BSMI_ERR_INVALID, "winograd input transform: only a factor-2 upsampling can be fused");
       const int par = 2 * (a.oy[q] & 1) + (a.ox[q] & 1);
       if (m == 4) {
@@ -836,7 +973,8 @@ int launch_wino_in(const WinoInArgs& a, hipStream_t s) {
       else if (par == 2) hipLaunchKernelGGL((wino_in_up_kernel<1, 0>), grid, dim3(256), 0, s, a, q, total);
       else hipLaunchKernelGGL((wino_in_up_kernel<1, 1>), grid, dim3(256), 0, s, a, q, total);
     } else if (m == 4) {
-      hipLaunchKernelGGL(wino4_in_kernel, grid, dim3(256), 0, s, a, q, total, S, nseg);
+      if (a.wz) hipLaunchKernelGGL(wino4_in_kernel<true>, grid, dim3(256), 0, s, a, q, total, S, nseg);
+      else hipLaunchKernelGGL(wino4_in_kernel<false>, grid, dim3(256), 0, s, a, q, total, S, nseg);
     } else {
       hipLaunchKernelGGL(wino_in_kernel, grid, dim3(256), 0, s, a, q, total);
     }
@@ -859,9 +997,12 @@ int launch_wino_out(const WinoOutArgs& a, hipStream_t s) {
     if (a.lH < 1 || a.lW < 1 || (int64_t)a.lH * a.lW * a.brow >= ((int64_t)1 << 31) || a.brow < a.Co || a.btap < a.Co || a.boy < 0 || a.box < 0 || a.boy + Ho + 2 > 2 * a.lH || a.box + Wo + 2 > 2 * a.lW)
       BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: the sums below the upsampling do not cover the stage's input");
   }
-  const size_t total = (size_t)a.Do * a.Ty * a.Tx * (a.Co / (m == 4 ? 4 : 8));
+  if (a.wz && (m != 4 || a.low || a.below || a.pool)) BSMI_FAIL(BSMI_ERR_INVALID, "winograd output transform: the z transform needs F(4x4) and takes no low-resolution sums and no pooled output");
+  const size_t total = (size_t)(a.wz ? (a.Do + 1) / 2 : a.Do) * a.Ty * a.Tx * (a.Co / (m == 4 ? 4 : 8));
   const dim3 grid((unsigned)((total + 255) / 256));
-  if (m == 4) {
+  if (a.wz) {
+    hipLaunchKernelGGL(wino4z_out_kernel, grid, dim3(256), 0, s, a, total);
+  } else if (m == 4) {
     if (a.below) {
       const int par = 2 * (a.boy & 1) + (a.box & 1);
       if (par == 0) hipLaunchKernelGGL((wino4_out_kernel<false, false, 0>), grid, dim3(256), 0, s, a, total);
@@ -877,10 +1018,10 @@ int launch_wino_out(const WinoOutArgs& a, hipStream_t s) {
   return BSMI_OK;
 }
 
-void wino_units(int Cv, std::vector<WinoUnit>& out) {
+void wino_units(int Cv, std::vector<WinoUnit>& out, int taps) {
   out.clear();
   for (int c32 = 0; c32 < Cv; c32 += 32)
-    for (int kz = 0; kz < 3; ++kz)
+    for (int kz = 0; kz < taps; ++kz)
       for (int j = 0; j < kUnitsPerStep; ++j) {
         const int c = c32 + 16 * j;
         if (c < Cv) out.push_back(WinoUnit{kz, c, false});
@@ -905,9 +1046,9 @@ static inline float host_bf16_f32(uint16_t b) {
 }
 
 void wino_pack_weights(const float* w, int cout, int cin, const std::vector<int>& cin_of_v, int Npad, const std::vector<WinoUnit>& units,
-                       std::vector<uint16_t>& packed, size_t& image_elems, size_t& batch_elems, int m) {
+                       std::vector<uint16_t>& packed, size_t& image_elems, size_t& batch_elems, int m, bool wz) {
   const size_t nsteps = units.size() / kUnitsPerStep;
-  const int T = m + 2, nbatch = T * T;
+  const int T = m + 2, nbatch = T * T * (wz ? kWinoZ : 1);
   batch_elems = nsteps * (size_t)Npad * 32;
   image_elems = nbatch * batch_elems + (size_t)kWeightRowSlack * 32;
   packed.assign(2 * image_elems, 0);
@@ -927,17 +1068,22 @@ void wino_pack_weights(const float* w, int cout, int cin, const std::vector<int>
       for (int kk = 0; kk < 16; ++kk) {
         const int c = cin_of_v[un.vc0 + kk];
         if (c < 0) continue;
-        const float* g = w + (((size_t)n * cin + c) * 3 + un.kz) * 9;  // [ky][kx]
-        double t[6][3];
-        for (int xi = 0; xi < T; ++xi)
-          for (int kx = 0; kx < 3; ++kx) t[xi][kx] = G[xi][0] * g[kx] + G[xi][1] * g[3 + kx] + G[xi][2] * g[6 + kx];
+        const float* g = w + (((size_t)n * cin + c) * 3 + un.kz) * 9;  // [ky][kx]; wz: the unit's kz is 0, all three taps
+        double t[3][6][3];
+        for (int kz = 0; kz < (wz ? 3 : 1); ++kz)
+          for (int xi = 0; xi < T; ++xi)
+            for (int kx = 0; kx < 3; ++kx) t[kz][xi][kx] = G[xi][0] * g[9 * kz + kx] + G[xi][1] * g[9 * kz + 3 + kx] + G[xi][2] * g[9 * kz + 6 + kx];
         for (int xi = 0; xi < T; ++xi)
           for (int nu = 0; nu < T; ++nu) {
-            const float v = (float)(t[xi][0] * G[nu][0] + t[xi][1] * G[nu][1] + t[xi][2] * G[nu][2]);
-            const size_t idx = (size_t)(T * xi + nu) * batch_elems + (s * Npad + n) * 32 + j * 16 + kk;
-            const uint16_t hi = host_bf16(v);
-            packed[idx] = hi;
-            packed[image_elems + idx] = host_bf16(v - host_bf16_f32(hi));
+            double u[3];
+            for (int kz = 0; kz < (wz ? 3 : 1); ++kz) u[kz] = t[kz][xi][0] * G[nu][0] + t[kz][xi][1] * G[nu][1] + t[kz][xi][2] * G[nu][2];
+            for (int e = 0; e < (wz ? kWinoZ : 1); ++e) {
+              const float v = wz ? (float)(G2[e][0] * u[0] + G2[e][1] * u[1] + G2[e][2] * u[2]) : (float)u[0];
+              const size_t idx = (size_t)(T * T * e + T * xi + nu) * batch_elems + (s * Npad + n) * 32 + j * 16 + kk;
+              const uint16_t hi = host_bf16(v);
+              packed[idx] = hi;
+              packed[image_elems + idx] = host_bf16(v - host_bf16_f32(hi));
+            }
           }
       }
     }
@@ -960,7 +1106,8 @@ struct WinoPackDev {
 };
 // T (4 or 6) is a compile-time constant: t[][] and the rows of G are indexed by unrolled loops only and stay in registers.
 // (With T read from the arguments they lived in a 160-byte scratch segment; no kernel of the network engine has one now.)
-template <int T>
+// WZ: the z transform of the weights as well (wino_pack_weights, wz), the host's operations in the host's order.
+template <int T, bool WZ = false>
 __global__ __launch_bounds__(256) void wino_pack_kernel(const WinoPackDev a) {
 #pragma clang fp contract(off)
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -976,37 +1123,51 @@ __global__ __launch_bounds__(256) void wino_pack_kernel(const WinoPackDev a) {
   const int c = a.cin_of_v[a.unit_vc0[u] + kk];
   if (c < 0) return;
   const float* g = a.w + (((size_t)n * a.cin + c) * 3 + kz) * 9;
-  double gd[9];
+  constexpr int NZ = WZ ? 3 : 1;  // z taps one thread transforms (WZ: the unit's kz is 0)
+  double gd[NZ][9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) gd[k] = (double)g[k];
+  for (int kz = 0; kz < NZ; ++kz)
+#pragma unroll
+    for (int k = 0; k < 9; ++k) gd[kz][k] = (double)g[9 * kz + k];
   constexpr double aa = 0.70710678118654752440, bb = 1.41421356237309504880;
   constexpr double G4[6][3] = {{1, 0, 0}, {2. / 3, 2. / 3 * aa, 1. / 3}, {2. / 3, -2. / 3 * aa, 1. / 3}, {1. / 12, bb / 12, 1. / 6}, {1. / 12, -bb / 12, 1. / 6}, {0, 0, 1}};
   constexpr double G2[6][3] = {{1, 0, 0}, {.5, .5, .5}, {.5, -.5, .5}, {0, 0, 1}, {0, 0, 0}, {0, 0, 0}};
-  double t[T][3];
+  double t[NZ][T][3];
 #pragma unroll
-  for (int xi = 0; xi < T; ++xi)
+  for (int kz = 0; kz < NZ; ++kz)
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      const double g0 = T == 6 ? G4[xi][0] : G2[xi][0], g1 = T == 6 ? G4[xi][1] : G2[xi][1], g2 = T == 6 ? G4[xi][2] : G2[xi][2];
-      t[xi][kx] = g0 * gd[kx] + g1 * gd[3 + kx] + g2 * gd[6 + kx];
-    }
+    for (int xi = 0; xi < T; ++xi)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const double g0 = T == 6 ? G4[xi][0] : G2[xi][0], g1 = T == 6 ? G4[xi][1] : G2[xi][1], g2 = T == 6 ? G4[xi][2] : G2[xi][2];
+        t[kz][xi][kx] = g0 * gd[kz][kx] + g1 * gd[kz][3 + kx] + g2 * gd[kz][6 + kx];
+      }
 #pragma unroll
   for (int xi = 0; xi < T; ++xi)
 #pragma unroll
     for (int nu = 0; nu < T; ++nu) {
       const double g0 = T == 6 ? G4[nu][0] : G2[nu][0], g1 = T == 6 ? G4[nu][1] : G2[nu][1], g2 = T == 6 ? G4[nu][2] : G2[nu][2];
-      const float v = (float)(t[xi][0] * g0 + t[xi][1] * g1 + t[xi][2] * g2);
-      const size_t idx = (size_t)(T * xi + nu) * a.batch_elems + (s * a.Npad + n) * 32 + j * 16 + kk;
-      const uint16_t hi = to_bf16(v);
-      a.image[idx] = hi;
-      a.image[a.image_elems + idx] = to_bf16(v - __uint_as_float((uint32_t)hi << 16));
+      double u[NZ];
+#pragma unroll
+      for (int kz = 0; kz < NZ; ++kz) u[kz] = t[kz][xi][0] * g0 + t[kz][xi][1] * g1 + t[kz][xi][2] * g2;
+#pragma unroll
+      for (int e = 0; e < (WZ ? kWinoZ : 1); ++e) {
+        float v;
+        if constexpr (WZ) v = (float)(G2[e][0] * u[0] + G2[e][1] * u[1] + G2[e][2] * u[2]);
+        else v = (float)u[0];
+        const size_t idx = (size_t)(T * T * e + T * xi + nu) * a.batch_elems + (s * a.Npad + n) * 32 + j * 16 + kk;
+        const uint16_t hi = to_bf16(v);
+        a.image[idx] = hi;
+        a.image[a.image_elems + idx] = to_bf16(v - __uint_as_float((uint32_t)hi << 16));
+      }
     }
 }
 
 int wino_pack_weights_dev(const float* w, int cout, int cin, const std::vector<int>& cin_of_v, int Npad, const std::vector<WinoUnit>& units, int m,
-                          void** image_dev, size_t& image_elems, size_t& batch_elems) {
+                          void** image_dev, size_t& image_elems, size_t& batch_elems, bool wz) {
+  if (wz && m != 4) BSMI_FAIL(BSMI_ERR_INVALID, "winograd weights: the z transform exists for F(4x4) only");
   const size_t nsteps = units.size() / kUnitsPerStep;
-  const int T = m + 2, nbatch = T * T;
+  const int T = m + 2, nbatch = T * T * (wz ? kWinoZ : 1);
   batch_elems = nsteps * (size_t)Npad * 32;
   image_elems = nbatch * batch_elems + (size_t)kWeightRowSlack * 32;
   uint16_t* image = nullptr;
@@ -1029,7 +1190,8 @@ int wino_pack_weights_dev(const float* w, int cout, int cin, const std::vector<i
     a.w = wd; a.cin_of_v = meta; a.unit_kz = meta + o_kz; a.unit_vc0 = meta + o_vc; a.image = image;
     a.image_elems = image_elems; a.batch_elems = batch_elems; a.cout = cout; a.cin = cin; a.Npad = Npad; a.nunits = (int)units.size(); a.T = T;
     const size_t total = nsteps * (size_t)cout * 32;
-    if (T == 6) hipLaunchKernelGGL(wino_pack_kernel<6>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, a);
+    if (wz) hipLaunchKernelGGL((wino_pack_kernel<6, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, a);
+    else if (T == 6) hipLaunchKernelGGL(wino_pack_kernel<6>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, a);
     else hipLaunchKernelGGL(wino_pack_kernel<4>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, a);
     err = hipGetLastError();
     if (err == hipSuccess) err = hipDeviceSynchronize();

@@ -248,7 +248,8 @@ class Model:
         forward materialised the step's output (debug_activation refuses the others), shape (D, H, W, C); conv steps also
         carry the state-dict prefix of their ConvPass, the conv index inside it, the kernel form that ran, its flags
         (fused-up, res-low, split-k), the GEMM tile's BN and the K-step count, and below_up: whether the stage convolves its
-        upsampled source below the upsampling (csrc/unet_rules.hip below_up_site)."""
+        upsampled source below the upsampling (csrc/unet_rules.hip below_up_site), and wino_z: whether a Winograd F(4x4) stage
+        is F(2,3) along z as well (csrc/unet_rules.hip wino_z_site)."""
         n = C.c_int()
         check(lib.bsmi_unet_debug_step_info(self._h, 0, None, C.byref(n)))
         out = []
@@ -259,7 +260,7 @@ class Model:
             if d["type"] == "conv":
                 d.update(prefix=si.prefix.decode(), conv=si.conv_index, form=_lib.CONV_FORMS[si.form],
                          flags=tuple(name for bit, name in _lib.STEP_FLAGS.items() if si.flags & bit), bn=si.bn, ksteps=si.ksteps,
-                         below_up=bool(si.flags & _lib.STEP_BELOW_UP))
+                         below_up=bool(si.flags & _lib.STEP_BELOW_UP), wino_z=bool(si.flags & _lib.STEP_WINO_Z))
             elif d["type"] == "head":
                 d.update(prefix=si.prefix.decode(), head=si.head)
             elif d["type"] in ("pool", "up"):

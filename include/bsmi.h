@@ -331,7 +331,8 @@ enum {
   BSMI_STEP_FUSED_UP = 1,      /* a source is read through an on-the-fly upsampling (the UP step before it is not materialised) */
   BSMI_STEP_RES_LOW = 2,       /* part of the residual branch runs as a GEMM of its own below the upsampling */
   BSMI_STEP_SPLIT_K = 4,       /* the launcher's rule sends (one of) the GEMM launches of this step to the persistent split-K form */
-  BSMI_STEP_BELOW_UP = 8       /* the 3x3x3 taps of the upsampled source run as nine (3,1,1) GEMM column groups below the upsampling */
+  BSMI_STEP_BELOW_UP = 8,      /* the 3x3x3 taps of the upsampled source run as nine (3,1,1) GEMM column groups below the upsampling */
+  BSMI_STEP_WINO_Z = 16        /* Winograd F(4x4) stage that is F(2,3) along z as well: 144 batches over pairs of output planes */
 };
 typedef struct {
   int32_t type;          /* BSMI_STEP_* */
@@ -349,6 +350,15 @@ typedef struct {
 } bsmi_unet_step_info;
 /* *n_steps (optional) receives the number of steps; info may be NULL to query it alone. */
 int bsmi_unet_debug_step_info(bsmi_unet *h, int step, bsmi_unet_step_info *info, int *n_steps);
+
+/* Development aid, host only (no device is touched): the transformed weights of a Winograd F(4x4) stage as the host packs
+ * them (the cross-check form of BSMI_WINO_PACK_HOST=1), for a stage whose V channels are its `cin` input channels padded to 16.
+ * w: OIDHW f32 [cout][cin][3][3][3]; wz != 0: the form that is F(2,3) along z as well (144 batches, batch 36 e + b, K = channels
+ * only), else 36 batches with the three z taps inside every 32-channel chunk.  The image is bf16 bit patterns, hi image then
+ * lo image of image_elems values each: value (batch, K-step s, column n, element k of the 32) at
+ * batch * batch_elems + (s * npad + n) * 32 + k.  out may be NULL to query the sizes; capacity in uint16 values. */
+int bsmi_debug_wino_pack_host(const float *w, int cout, int cin, int wz, uint16_t *out, uint64_t capacity,
+                              uint64_t *image_elems, uint64_t *batch_elems, int *npad, int *ksteps);
 
 /* Reflect-padded block extraction (gp.Pad(raw, None, mode="reflect") +
  * ArraySource ROI read, models/3d_affs/predict.py:145-148): copies the window

@@ -215,15 +215,15 @@ int bsmi_mws_cluster(uint64_t n_nodes, const uint64_t* edges, const double* scor
     if (edges[2 * i] >= n_nodes || edges[2 * i + 1] >= n_nodes)
       BSMI_FAIL(BSMI_ERR_INVALID, "edge %llu names node %llu / %llu of %llu", (unsigned long long)i, (unsigned long long)edges[2 * i],
                 (unsigned long long)edges[2 * i + 1], (unsigned long long)n_nodes);
-  std::vector<uint64_t> order(m);
-  std::iota(order.begin(), order.end(), (uint64_t)0);
+  // 0 and NaN are no edges and leave before the sort: with NaN among them `|a| > |b|` is no strict weak ordering
+  // (NaN would be equivalent to everything) and the real edges come out of order
+  std::vector<uint64_t> order;
+  order.reserve(m);
+  for (uint64_t i = 0; i < m; ++i)
+    if (std::fabs(scores[i]) > 0.0) order.push_back(i);
   std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return std::fabs(scores[a]) > std::fabs(scores[b]); });
   MutexForest f(n_nodes);
-  for (uint64_t i : order) {
-    const double w = scores[i];
-    if (!(std::fabs(w) > 0.0)) continue;  // 0 and NaN: no edge
-    f.edge((uint32_t)edges[2 * i], (uint32_t)edges[2 * i + 1], w < 0.0);
-  }
+  for (uint64_t i : order) f.edge((uint32_t)edges[2 * i], (uint32_t)edges[2 * i + 1], scores[i] < 0.0);
   f.labels(labels_out);
   return BSMI_OK;
 }

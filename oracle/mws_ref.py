@@ -14,7 +14,9 @@ and from this image, and the reference holds no fixtures for them, so this file 
   * a voxel's label is 1 + the smallest voxel index of its cluster (any labelling of the same partition is
     equivalent: results are compared after ID remap).
 
-Deliberately naive (dict of sets, python loops): small cases only.
+Deliberately naive (dict of sets, python loops): a few thousand voxels at the most.  For product-sized cases
+tests/mws_fast_ref.py lists and orders the edges with array operations and keeps this file's sweep (`_Forest`);
+tests/test_mws_fast_ref_cpu.py holds it equal to the loops below.
 """
 import numpy as np
 

@@ -49,3 +49,31 @@ def test_library_graph_clustering_equals_restatement():
         e = e[e[:, 0] != e[:, 1]] if m else e
         s = np.round(rng.standard_normal(len(e)), 1)
         assert np.array_equal(mws_cluster(n, e, s), mws_ref.mws_cluster(n, e, s))
+
+
+def nonfinite_scores(rng, m):
+    """tie-rich scores with 15 % NaN and some +-inf and +-0.0"""
+    s = np.round(rng.standard_normal(m), 1)
+    r = rng.random(m)
+    s[r < 0.15] = np.nan
+    for j, v in enumerate([np.inf, -np.inf, 0.0, -0.0]):
+        s[(r >= 0.15 + 0.02 * j) & (r < 0.17 + 0.02 * j)] = v
+    return s
+
+
+def test_library_graph_clustering_with_nonfinite_scores():
+    """NaN is no edge, like 0; +-inf are the strongest edges.  With NaN among the scores `|a| > |b|` is no strict weak
+    ordering (NaN is "equivalent" to everything), so the library must drop the non-edges before it sorts: sorting all of them
+    left the real edges out of order.  The restatement's own sort has the same weakness, so it gets NaN replaced by 0."""
+    from bootstrapper_amd.post.mws import mws_cluster
+    rng = np.random.default_rng(1)
+    for n, m in [(2, 1), (30, 200), (200, 3000), (200, 3000), (200, 3000)]:
+        e = rng.integers(0, n, size=(m, 2))
+        e = e[e[:, 0] != e[:, 1]]
+        s = nonfinite_scores(rng, len(e))
+        if m > 1:
+            assert np.isnan(s).sum() > 0.1 * m and np.isinf(s).any() and (s == 0).any()
+        assert np.array_equal(mws_cluster(n, e, s), mws_ref.mws_cluster(n, e, np.where(np.isnan(s), 0.0, s)))
+    for v in (np.nan, 0.0, -0.0):
+        assert np.array_equal(mws_cluster(4, [[0, 1], [1, 2], [2, 3]], [v] * 3), np.arange(1, 5, dtype=np.uint64))
+    assert mws_cluster(4, [[0, 1], [1, 2], [2, 3], [0, 2]], [0.9, np.inf, 0.7, -np.inf]).tolist() == [1, 2, 2, 2]

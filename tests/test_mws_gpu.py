@@ -73,6 +73,12 @@ def test_graph_mutex_watershed_and_pair_affinities():
     e = e[e[:, 0] != e[:, 1]]
     s = np.round(rng.standard_normal(len(e)), 1)   # ties and exact zeros included
     assert np.array_equal(mws_cluster(n, e, s), mws_ref.mws_cluster(n, e, s))
+    s2 = s.copy()                                  # NaN (no edge, like 0) and +-inf (the strongest edges) among them
+    r = np.random.default_rng(12).random(len(s2))
+    s2[r < 0.15] = np.nan
+    s2[(r >= 0.15) & (r < 0.17)] = np.inf
+    s2[(r >= 0.17) & (r < 0.19)] = -np.inf
+    assert np.array_equal(mws_cluster(n, e, s2), mws_ref.mws_cluster(n, e, np.where(np.isnan(s2), 0.0, s2)))
     assert np.array_equal(mws_cluster(5, np.zeros((0, 2)), np.zeros(0)), np.arange(1, 6, dtype=np.uint64))
     with pytest.raises(RuntimeError):
         mws_cluster(3, [[0, 7]], [1.0])

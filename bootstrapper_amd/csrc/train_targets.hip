@@ -247,7 +247,9 @@ int bsmi_train_affinity_targets_roi(int device, int64_t* labels_dev, const uint8
 // of normalised 1-D Gaussians truncated at 3 sigma (scipy.ndimage.gaussian_filter(mode="constant", truncate=3.0)).
 // Channels: mean - c(s) (z, y, x) / sigma * 0.5 + 0.5 | variances / sigma^2 | Pearson zy, zx, yx * 0.5 + 0.5 | count;
 // clipped to [0, 1]; background voxels are all zero.  Coordinates are taken relative to s (the differences are what
-// enters; the library's absolute float32 coordinates only add rounding).
+// enters; the library's absolute float32 coordinates only add rounding).  A label with no tap in the window (count 0: an
+// object thinner than df that misses the sub-sampled grid) has mean 0 in the library's absolute coordinates and covariance
+// 0: its offset is minus the position of s, the variances are the 1e-3 floor, the Pearson channels 0.5.
 struct LsdArgs {
   const int64_t* labels;  // [D][H][W] with the context the window needs
   int D, H, W;
@@ -304,6 +306,13 @@ __global__ void lsd_targets_kernel(LsdArgs a, const uint8_t* __restrict__ unl, f
       pe[0] /= sqrt(var[0] * var[1]);
       pe[1] /= sqrt(var[0] * var[2]);
       pe[2] /= sqrt(var[1] * var[2]);
+      if (n == 0) {
+        // a label absent from the window gets the lsd package's values: mean 0 in absolute coordinates of the array, i.e. an
+        // offset of minus the cell's position (as lsd2d_targets_kernel does); the covariance above is that of no tap: 0
+        mean[0] = -(double)sz * a.step[0];
+        mean[1] = -(double)sy * a.step[1];
+        mean[2] = -(double)sx * a.step[2];
+      }
       for (int i = 0; i < 3; ++i) {
         out[i] = (float)(mean[i] / a.sigma[i] * 0.5 + 0.5);
         out[3 + i] = (float)(var[i] / ((double)a.sigma[i] * a.sigma[i]));

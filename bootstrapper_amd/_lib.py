@@ -202,6 +202,9 @@ def _load():
         "bsmi_unet_profile_executed": (i32, [p, C.POINTER(C.c_double), C.c_int]),
         "bsmi_debug_lds_canary": (i32, [i32, i32, i32, vp, vp]),
         "bsmi_debug_check_guards": (i32, []),
+        "bsmi_debug_torch_malloc": (vp, [C.c_ssize_t, i32, vp]),
+        "bsmi_debug_torch_free": (None, [vp, C.c_ssize_t, vp]),
+        "bsmi_debug_guard_selftest": (i32, []),
         "bsmi_stream_create_cu_mask": (i32, [C.c_int, vp, C.c_int, C.POINTER(C.c_void_p)]),
         "bsmi_stream_destroy": (i32, [C.c_int, vp]),
         "bsmi_eval_create": (i32, [i32, C.c_uint64, C.POINTER(p)]),

@@ -8,6 +8,10 @@
 namespace bsmi {
 hipError_t guarded_malloc(void** p, size_t bytes, const char* file, int line);
 hipError_t guarded_free(void* p);
+// For scratch that the product path takes from a stream (hipMallocAsync): is BSMI_GUARD_MB set, and the release that waits for
+// the stream, reads the two zones back, reports and counts the damaged ones for bsmi_debug_check_guards(), then frees.
+bool guards_on();
+hipError_t guarded_free_checked(void* p, hipStream_t s);
 }  // namespace bsmi
 
 #define hipMalloc(p, n) ::bsmi::guarded_malloc((void**)(p), (n), __FILE__, __LINE__)

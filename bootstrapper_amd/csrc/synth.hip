@@ -22,6 +22,7 @@
 #include "../../include/bsmi.h"
 #include "common.h"
 #include "seg_internal.h"
+#include "dev_guard.h"  // last: routes hipMalloc / hipFree through the guarded allocator (BSMI_GUARD_MB)
 
 struct bsmi_synth {
   int device = 0;

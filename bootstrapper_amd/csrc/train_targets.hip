@@ -5,6 +5,13 @@
 #include <vector>
 
 #include "common.h"
+#include "dev_guard.h"  // last
+
+// Scratch comes from the stream.  With BSMI_GUARD_MB set it lies between guard zones instead, and its release waits for the stream,
+// reads the zones back and counts the damaged ones for bsmi_debug_check_guards() (dev_guard.hip); the kernels are the same.
+#define SCRATCH_MALLOC_ASYNC(p, n, s) \
+  (::bsmi::guards_on() ? ::bsmi::guarded_malloc((void**)(p), (n), __FILE__, __LINE__) : hipMallocAsync((void**)(p), (n), (s)))
+#define SCRATCH_FREE_ASYNC(p, s) (::bsmi::guards_on() ? ::bsmi::guarded_free_checked((p), (s)) : hipFreeAsync((p), (s)))
 
 namespace bsmi {
 
@@ -174,7 +181,7 @@ int bsmi_train_affinity_targets(int device, int64_t* labels_dev, const uint8_t* 
   // scratch on the stream: the grown labels (the erosion reads its neighbours' old values) and two counters
   int64_t* grown = nullptr;
   unsigned long long* counts = nullptr;
-  BSMI_HIP(hipMallocAsync((void**)&grown, nvox * sizeof(int64_t) + 2 * sizeof(unsigned long long), s));
+  BSMI_HIP(SCRATCH_MALLOC_ASYNC(&grown, nvox * sizeof(int64_t) + 2 * sizeof(unsigned long long), s));
   counts = (unsigned long long*)(grown + nvox);
   BSMI_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s));
   const int bs = 256;
@@ -186,7 +193,7 @@ int bsmi_train_affinity_targets(int device, int64_t* labels_dev, const uint8_t* 
   hipLaunchKernelGGL(balance_kernel, dim3((unsigned)std::min<size_t>((total + bs - 1) / bs, 65535)), dim3(bs), 0, s, affs_dev, weights_dev, total,
                      counts, clip_min, clip_max);
   BSMI_HIP(hipGetLastError());
-  BSMI_HIP(hipFreeAsync(grown, s));
+  BSMI_HIP(SCRATCH_FREE_ASYNC(grown, s));
   return BSMI_OK;
 }
 
@@ -213,7 +220,7 @@ int bsmi_train_affinity_targets_roi(int device, int64_t* labels_dev, const uint8
   hipStream_t s = (hipStream_t)stream;
   // scratch on the stream: the grown labels (the erosion reads its neighbours' old values) and two counters per sample
   int64_t* grown = nullptr;
-  BSMI_HIP(hipMallocAsync((void**)&grown, nvox * sizeof(int64_t) + 2 * (size_t)S * sizeof(unsigned long long), s));
+  BSMI_HIP(SCRATCH_MALLOC_ASYNC(&grown, nvox * sizeof(int64_t) + 2 * (size_t)S * sizeof(unsigned long long), s));
   unsigned long long* counts = (unsigned long long*)(grown + nvox);
   BSMI_HIP(hipMemsetAsync(counts, 0, 2 * (size_t)S * sizeof(unsigned long long), s));
   const int bs = 256;
@@ -234,7 +241,7 @@ int bsmi_train_affinity_targets_roi(int device, int64_t* labels_dev, const uint8
   hipLaunchKernelGGL(balance_roi_kernel, dim3((unsigned)std::min<size_t>((total + bs - 1) / bs, 65535)), dim3(bs), 0, s, affs_dev, weights_dev,
                      total, nroi, S, counts, clip_min, clip_max);
   BSMI_HIP(hipGetLastError());
-  BSMI_HIP(hipFreeAsync(grown, s));
+  BSMI_HIP(SCRATCH_FREE_ASYNC(grown, s));
   return BSMI_OK;
 }
 
@@ -368,7 +375,7 @@ int bsmi_train_lsd_targets(int device, const int64_t* labels_dev, const uint8_t*
   a.rz = r[0]; a.ry = r[1]; a.rx = r[2];
   float* wdev = nullptr;
   const size_t nw = w[0].size() + w[1].size() + w[2].size();
-  BSMI_HIP(hipMallocAsync((void**)&wdev, nw * sizeof(float), s));
+  BSMI_HIP(SCRATCH_MALLOC_ASYNC(&wdev, nw * sizeof(float), s));
   std::vector<float> all;
   for (int i = 0; i < 3; ++i) all.insert(all.end(), w[i].begin(), w[i].end());
   // the host vector must outlive the asynchronous copy: copy synchronously (a few hundred bytes)
@@ -379,7 +386,7 @@ int bsmi_train_lsd_targets(int device, const int64_t* labels_dev, const uint8_t*
   hipLaunchKernelGGL(lsd_targets_kernel, dim3((unsigned)std::min<size_t>((nout + 127) / 128, 65535)), dim3(128), 0, s, a, unlabelled_dev, lsds_dev,
                      weights_dev);
   BSMI_HIP(hipGetLastError());
-  BSMI_HIP(hipFreeAsync(wdev, s));
+  BSMI_HIP(SCRATCH_FREE_ASYNC(wdev, s));
   return BSMI_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <sys/types.h> /* ssize_t */
 
 #ifdef __cplusplus
 extern "C" {
@@ -301,8 +302,22 @@ int bsmi_debug_lds_canary(int lds_bytes, int blocks, int spins, unsigned long lo
 /* Development aid: with BSMI_GUARD_MB=<n> in the environment every device allocation of the network engine, the training state and
  * the segmentation engines lies between
  * two n-MiB zones of 0xFF bytes (csrc/dev_guard.h): a read past a buffer that reaches a result turns it into NaNs, and this
- * call counts the zones something WROTE into (0 = intact, each hit reported on stderr; -1 = HIP error; 0 when unset). */
+ * call counts the zones something WROTE into (0 = intact, each hit reported on stderr; -1 = HIP error; 0 when unset): those of
+ * the live allocations plus those that checked releases (below, and the stream scratch of the training targets) have counted
+ * since the last call. */
 int bsmi_debug_check_guards(void);
+/* The same guards around every tensor of torch's: the pair that torch.cuda.memory.CUDAPluggableAllocator(libbsmi.so, ...) takes
+ * (`stream` is a hipStream_t).  malloc gives exactly `size` bytes between two zones, the far one beginning at byte `size`, on
+ * `device` (the caller's device is restored); free waits for the device, reads that allocation's zones, reports each damaged one
+ * on stderr ("torch tensor of N bytes"), adds them to the count of bsmi_debug_check_guards() and frees.  It never aborts, and
+ * gives the check up quietly after a HIP error (interpreter shutdown).  Unset: plain hipMalloc / hipFree.
+ * tests/test_redzones_gpu.py runs the parity tests of the kernels that work in the caller's tensors this way. */
+void *bsmi_debug_torch_malloc(ssize_t size, int device, void *stream);
+void bsmi_debug_torch_free(void *ptr, ssize_t size, void *stream);
+/* Does the checker see what it must?  One guarded buffer of 1000 bytes; hipMemset writes single bytes into the buffer's own zones
+ * (just past the end, just before the start, the outermost byte of each zone); the checker must name exactly those zones and
+ * offsets, and a checked release must count them.  0 = it does; -1 = BSMI_GUARD_MB unset or a HIP error; > 0 = the failed step. */
+int bsmi_debug_guard_selftest(void);
 
 /* Development aid: the output tensor of launch `step` of the last forward (launch order as in
  * bsmi_unet_profile_read), as float32 channels-last [D][H][W][C] on the host, whatever the precision mode stores

@@ -145,6 +145,61 @@ def test_agglomeration_bit_exact_vs_oracle(shape, sigma):
     assert len(np.unique(ref[2])) < len(np.unique(frags))
 
 
+def test_ws_fragments_without_seeds_entry_equals_the_wrapper_s():
+    """bsmi_ws_fragments_u8, which no wrapper of the package calls, gives what SegEngine.ws_fragments (the seeds entry) gives"""
+    import ctypes as C
+    from bootstrapper_amd import _lib
+    from bootstrapper_amd.post.engine import SegEngine
+    shape = (4, 50, 70)
+    a = torch.from_numpy(_blobby(np.random.default_rng(2), shape, (0, 1, 1))).cuda()
+    eng = SegEngine(shape)
+    want, want_max = eng.ws_fragments(a, True, 4)
+    frags = torch.empty(shape, dtype=torch.int64, device="cuda")
+    mx = torch.zeros(1, dtype=torch.int64, device="cuda")
+    _lib.check(_lib.lib.bsmi_ws_fragments_u8(eng._h, C.c_void_p(a.data_ptr()), _lib.i64x3(shape), 1, 4, C.c_void_p(frags.data_ptr()),
+                                             C.c_void_p(mx.data_ptr()), eng._stream()))
+    eng.status()
+    assert int(mx.item()) == int(want_max.item()) > 1 and torch.equal(frags, want)
+
+
+@pytest.mark.parametrize("shape,sigma,epsilon", [((4, 50, 70), (0, 1, 1), 0.3), ((12, 64, 64), (1, 3, 3), 0.45)])
+def test_rag_agglomerate_in_place_equals_the_oracle(shape, sigma, epsilon):
+    """SegEngine.rag_agglomerate (bsmi_rag_agglomerate_u8, the epsilon agglomeration of the fragments task) on its own: the only other
+    test of it goes through SlabSegmenter (tests/test_volume_gpu.py)"""
+    from bootstrapper_amd.post.engine import SegEngine
+    from oracle import seg_ref as S
+    from oracle.blockwise_ref import epsilon_agglomerate
+    affs = _blobby(np.random.default_rng(shape[0] + 1), shape, sigma)
+    frags, _ = S.ws_fragments_u8(affs, True, 4)
+    ref = epsilon_agglomerate(affs, frags, epsilon)
+    eng = SegEngine(shape)
+    t = torch.from_numpy(frags.astype(np.int64)).cuda()
+    assert eng.rag_agglomerate(torch.from_numpy(affs).cuda(), t, epsilon, 256) is t
+    eng.status()
+    assert np.array_equal(t.cpu().numpy().view(np.uint64), ref)
+    assert 1 < len(np.unique(ref)) < len(np.unique(frags))          # some fragments merged, not all
+
+
+@pytest.mark.parametrize("shape,z0", [((5, 33, 47), 0), ((9, 64, 130), 7), ((1, 1, 1), 3)])
+def test_label_table_equals_numpy(shape, z0):
+    """SegEngine.label_table (bsmi_label_table_u64) on its own: ids above 2^32 and 2^63 up to the largest that the table takes (the two
+    above it are its empty and tombstone keys, reported as an overflow), a label in one voxel, background"""
+    from bootstrapper_amd.post.engine import SegEngine
+    rng = np.random.default_rng(shape[1])
+    ids = np.array([0, 1, 2, 5, (1 << 32) + 3, (1 << 63) + 11, (1 << 64) - 3], dtype=np.uint64)
+    lab = ids[rng.integers(0, 4, shape)]
+    z, y, x = np.indices(shape)
+    lab[(z >= shape[0] // 2) & (y % 5 == 0)] = ids[4]
+    lab[(z == shape[0] - 1) & (x % 7 == 3)] = ids[5]
+    lab[0, 0, 0] = ids[6]
+    got_ids, got_n, got_lo, got_hi = SegEngine(shape).label_table(torch.from_numpy(lab.view(np.int64)).cuda(), z0)
+    want = np.unique(lab[lab != 0])
+    assert got_ids.dtype == np.uint64 and np.array_equal(got_ids, want)
+    for k, v in enumerate(want):
+        zs = np.nonzero((lab == v).any(axis=(1, 2)))[0]
+        assert got_n[k] == int((lab == v).sum()) and got_lo[k] == z0 + zs[0] and got_hi[k] == z0 + zs[-1], (int(v), k)
+
+
 def test_agglomeration_edge_cases():
     from bootstrapper_amd.post.engine import SegEngine
     from oracle import seg_ref as S

@@ -17,10 +17,19 @@ STRUCTS = {"star": S.star(5), "disk": S.disk(3), "ellipse": S.ellipse(4, 2), "cr
 
 
 @pytest.fixture(scope="module")
-def eng():
-    e = S.SynthEngine((12, 40, 65), 0)
-    yield e
-    e.close()
+def engines():
+    """engines(shape): an engine made for exactly that shape, so that an index past the case's extent leaves the workspace (and, under
+    tests/test_redzones_gpu.py, lands in a guard zone); one per shape for the whole module"""
+    made = {}
+
+    def get(shape):
+        shape = tuple(int(v) for v in shape)
+        if shape not in made:
+            made[shape] = S.SynthEngine(shape, 0)
+        return made[shape]
+    yield get
+    for e in made.values():
+        e.close()
 
 
 def dev(a):
@@ -52,14 +61,16 @@ def blocks(shape, holes=True):
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("kind", sorted(STRUCTS))
 @pytest.mark.parametrize("iterations", [1, 10])
-def test_dilation(eng, shape, kind, iterations):
+def test_dilation(engines, shape, kind, iterations):
+    eng = engines(shape)
     pts = border_points(shape, 3)
     idx, its = np.zeros(shape[0], dtype=np.int32), np.full(shape[0], iterations, dtype=np.int32)
     got = host(eng.dilate_points(shape, pts, [STRUCTS[kind]], idx, its))
     assert np.array_equal(got, R.dilate_points(shape, pts, [STRUCTS[kind]], idx, its))
 
 
-def test_dilation_per_section_tables_and_refusal(eng):
+def test_dilation_per_section_tables_and_refusal(engines):
+    eng = engines((9, 33, 65))
     shape = (9, 33, 65)
     pts = border_points(shape, 4)
     structs = list(STRUCTS.values())
@@ -100,8 +111,9 @@ def tube_cases():
 
 
 @pytest.mark.parametrize("name", ["plan", "far", "section"])
-def test_tubes_branch(eng, tube_cases, name):
+def test_tubes_branch(engines, tube_cases, name):
     fg, lab, n, ex, (final, m) = tube_cases[name]
+    eng = engines(fg.shape)
     got, gn = eng.label(dev(fg))
     assert gn == n and np.array_equal(host(got), lab)
     assert np.array_equal(host(eng.expand(dev(lab), fg.shape[0], n + 1)), ex)
@@ -109,8 +121,9 @@ def test_tubes_branch(eng, tube_cases, name):
     assert gm == m and np.array_equal(host(got), final)
 
 
-def test_expand_tie_rule(eng):
+def test_expand_tie_rule(engines):
     """features at equal distances along every axis and diagonally: the lowest raster index wins"""
+    eng = engines((5, 9, 9))
     lab = np.zeros((5, 9, 9), dtype=np.int32)
     for k, (z, y, x) in enumerate([(2, 4, 0), (2, 4, 8), (2, 0, 4), (2, 8, 4), (0, 4, 4), (4, 4, 4), (0, 0, 0), (4, 8, 8)]):
         lab[z, y, x] = k + 1
@@ -121,7 +134,8 @@ def test_expand_tie_rule(eng):
 
 
 @pytest.mark.parametrize("shape", SHAPES)
-def test_gaussian_against_float64(eng, shape):
+def test_gaussian_against_float64(engines, shape):
+    eng = engines(shape)
     g = torch.Generator(device="cuda").manual_seed(5)
     noise = torch.rand(shape, generator=g, dtype=torch.float32, device="cuda")
     got = host(eng.gaussian(noise)).astype(np.float64)
@@ -137,7 +151,8 @@ def plateau_field(shape):
 
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("kind", ["blurred", "plateaus"])
-def test_argmax_filter_and_basins(eng, shape, kind):
+def test_argmax_filter_and_basins(engines, shape, kind):
+    eng = engines(shape)
     if kind == "blurred":       # the device's own field, read back: what the random branch sees
         g = torch.Generator(device="cuda").manual_seed(6)
         fld = eng.gaussian(torch.rand(shape, generator=g, dtype=torch.float32, device="cuda"))
@@ -154,14 +169,16 @@ def test_argmax_filter_and_basins(eng, shape, kind):
         assert (f.ravel()[want_pos] == f).sum() > m            # voxels tied with their window's maximum that are no roots
 
 
-def test_random_branch(eng):
+def test_random_branch(engines):
+    eng = engines((12, 40, 44))
     g = torch.Generator(device="cuda").manual_seed(8)
     noise = torch.rand((12, 40, 44), generator=g, dtype=torch.float32, device="cuda")
     f = host(eng.gaussian(noise))
     assert np.array_equal(host(eng.random_labels(noise)), R.basins(f, R.argmax_filter(f, S.PEAK_WINDOW))[0])
 
 
-def test_argmax_filter_even_window_and_mask(eng):
+def test_argmax_filter_even_window_and_mask(engines):
+    eng = engines((9, 33, 65))
     f = plateau_field((9, 33, 65))
     mask = (blocks((9, 33, 65)) % 3 != 0).astype(np.uint8)
     f *= mask
@@ -174,7 +191,8 @@ def test_argmax_filter_even_window_and_mask(eng):
 
 @pytest.mark.parametrize("anisotropy", [2, 5, 13])
 @pytest.mark.parametrize("drop3,drop5", [(False, False), (True, False), (True, True)])
-def test_finish(eng, anisotropy, drop3, drop5):
+def test_finish(engines, anisotropy, drop3, drop5):
+    eng = engines((12, 40, 44))
     lab = (blocks((12, 40, 44)) % 31).astype(np.int32)
     got = eng.finish(dev(lab), drop3, drop5, anisotropy)
     want = R.finish(lab, drop3, drop5, anisotropy)
@@ -184,7 +202,8 @@ def test_finish(eng, anisotropy, drop3, drop5):
 
 @pytest.mark.parametrize("shape", SHAPES)
 @pytest.mark.parametrize("max_steps", [1, 3])
-def test_grow_boundary(eng, shape, max_steps):
+def test_grow_boundary(engines, shape, max_steps):
+    eng = engines(shape)
     lab = blocks(shape)                    # its boxes touch every face of every section
     want = R.grow_boundary(lab, 1234567, max_steps)
     assert np.array_equal(host(eng.grow_boundary(dev(lab), 1234567, max_steps)), want)
@@ -205,7 +224,8 @@ def dumbbell():
     return lab
 
 
-def test_merge_stamp_present(eng):
+def test_merge_stamp_present(engines):
+    eng = engines((9, 33, 65))
     lab = blocks((9, 33, 65))
     t = dev(lab)
     assert eng.present(t) == [int(v) for v in np.unique(lab) if v]
@@ -224,7 +244,8 @@ def test_merge_stamp_present(eng):
 
 
 @pytest.mark.parametrize("window,sections", [(15, [4, 2]), (15, [0]), (50, [4]), (22, [8, 4])])
-def test_split(eng, window, sections):
+def test_split(engines, window, sections):
+    eng = engines((9, 33, 65))
     lab = dumbbell()
     scale = int(lab.max())
     want, m = R.split(lab, 7, window, sections, scale)
@@ -239,8 +260,9 @@ def test_split(eng, window, sections):
         assert (want[4][lab[4] == 7] == 12).any() and (want[4][lab[4] == 7] == 24).any()
 
 
-def test_obfuscate_follows_the_operation_list(eng):
+def test_obfuscate_follows_the_operation_list(engines):
     """the whole node with every operation likely: the same draws and the same labels as the restatement"""
+    eng = engines((9, 33, 65))
     lab = dumbbell() + blocks((9, 33, 65), holes=False) * (dumbbell() == 0)
     for seed in (1, 2, 3):
         got = eng.obfuscate(dev(lab), random.Random(seed), p_split=0.7, p_merge=0.7, p_artifact=0.7)

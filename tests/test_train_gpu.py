@@ -63,6 +63,26 @@ def test_training_step_vs_reference_goldens(golden_dir, tag, arithmetic):
     tr.close()
 
 
+def test_predictions_of_a_step_give_its_loss(golden_dir):
+    """Trainer.predictions (bsmi_unet_train_prediction) after one step on the smallest golden: the weighted mean squared error of what
+    it returns, in float64 (tests/bwd_ref.py), is the loss that the step reported -- to 1e-5, the gate that the loss is held to
+    against the golden above; the device sums some 10^4 float32 terms"""
+    import bwd_ref
+    from bootstrapper_amd.unet import Model
+    from bootstrapper_amd.training import Trainer
+    d = np.load(os.path.join(golden_dir, "train_affs_f4i2.npz"))
+    meta = json.loads(bytes(d["config"]).decode())
+    m = Model(_net_config(meta), precision="f32").load_state_dict({k[3:]: d[k] for k in d.files if k.startswith("w0:")})
+    tr = Trainer(m, meta["in_shape"], lr=meta["lr"], arithmetic="f32")
+    gt, w = d["gt0"][0], d["w0"][0]
+    loss = tr.forward_backward(torch.from_numpy(d["x"]).cuda(), [torch.from_numpy(gt).cuda()], [torch.from_numpy(w).cuda()])
+    (pred,) = tr.predictions().values()
+    assert pred.dtype == torch.float32 and tuple(pred.shape) == gt.shape
+    want = bwd_ref.weighted_mse(pred.cpu().numpy(), gt, w)[0]
+    assert abs(loss - want) < 1e-5 * max(1.0, abs(want)), (loss, want)
+    tr.close()
+
+
 @pytest.mark.parametrize("arithmetic", ["split-bf16", "f32"])
 def test_deterministic_step_is_bit_reproducible(arithmetic):
     """Trainer(deterministic=True): two runs of two steps (forward, backward, Adam) of the full net on the same inputs give the

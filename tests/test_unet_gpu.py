@@ -1,5 +1,6 @@
 """Parity of the HIP U-Net path (through the C ABI) with the oracle and with the golden
 vectors generated from the reference model code.  Needs an MI355X."""
+import ctypes
 import json
 import os
 
@@ -142,6 +143,20 @@ def test_extract_block_reflect_matches_numpy_pad():
         got = extract_block_reflect(torch.from_numpy(vol).cuda(), off, shape).cpu().numpy()
         sl = tuple(slice(o + p[0], o + p[0] + s) for o, p, s in zip(off, pad, shape))
         assert np.array_equal(got, ref_full[sl])
+
+
+def test_lds_canary_alone_counts_no_mismatch():
+    """bsmi_debug_lds_canary with nothing beside it: its workgroups find their own LDS as they left it, the caller's counter stays 0;
+    bad arguments are refused"""
+    from bootstrapper_amd import _lib
+    count = torch.zeros(1, dtype=torch.int64, device="cuda")
+    s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for lds_bytes, blocks in [(4, 1), (4096, 8), (32 * 1024, 3)]:
+        assert _lib.lib.bsmi_debug_lds_canary(lds_bytes, blocks, 1, ctypes.c_void_p(count.data_ptr()), s) == 0
+    torch.cuda.synchronize()
+    assert int(count.item()) == 0
+    for lds_bytes, blocks, ptr in [(0, 1, count.data_ptr()), (64 * 1024 + 4, 1, count.data_ptr()), (4096, 0, count.data_ptr()), (4096, 1, None)]:
+        assert _lib.lib.bsmi_debug_lds_canary(lds_bytes, blocks, 1, ctypes.c_void_p(ptr), s) == _lib.ERR_INVALID
 
 
 def test_forward_before_weights_fails_loudly():

@@ -32,9 +32,10 @@ was written, so parity is in distribution.  x is raw in [0, 1], sections are the
 Declared quirk: the reference's ImpulseNoiseAugment draws its locations with the node's p, not with the pixel_p its call
 site passes (gp/impulse_noise_augment.py:58), so the default of `impulse_pixel_p` is q = impulse_p, what the reference
 executes; setting the key gives the documented 0.05 or any other value.
-NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, SyntheticSource,
-3-D rotations.  The 2-D setups have their own chains, batched over the ten draws of a step (augment2d.py, the key `augment2d` and
-`intensity` inside it).
+NOT built: DefectAugment's deformation and artifacts (0 / absent in the reference's call), ClaheAugment, 3-D rotations.
+The 2-D setups have their own chains, batched over the ten draws of a step (augment2d.py, the key `augment2d` and `intensity`
+inside it).  The synthetic labels of the second-stage setups (train.SyntheticSource) run through the same map and the same
+two launches, with labels 0 outside the block (augment_labels.py, the key `label_augment`).
 """
 import ctypes as C
 import dataclasses
@@ -44,8 +45,8 @@ import numpy as np
 
 # what the trainer's log line names as missing: without `intensity`, and with it
 NOT_BUILT = "NoiseAugment, IntensityAugment, GammaAugment, ImpulseNoiseAugment, SmoothAugment and DefectAugment of raw"
-NOT_BUILT_WITH_INTENSITY = ("DefectAugment's deformation and artifacts; augmentation of synthetic labels (the 2-D setups have their own key, "
-                            "`augment2d`)")
+NOT_BUILT_WITH_INTENSITY = ("DefectAugment's deformation and artifacts (the 2-D setups have their own key, `augment2d`, the synthetic labels "
+                            "of the second-stage setups `label_augment`)")
 MAX_LATTICE_NODES = 4096   # csrc/augment.hip: 48 KiB of offsets in LDS
 MAX_RADIUS = 6             # csrc/augment_intensity.hip: taps of the smoothing kernel, int(4 sigma + 0.5)
 STAT_PARTS = 16            # include/bsmi.h: BSMI_AUG_STAT_PARTS
@@ -194,10 +195,11 @@ def lattice_shape(shape, spacing):
     return tuple(1 if i == 1 else int(math.ceil((i - 1) / sp)) + 3 for i, sp in zip(shape, spacing))
 
 
-def check_square(inp, out):
+def check_square(inp, out, key="augment"):
+    """key: the train config table whose `simple` the error names (`label_augment` for the synthetic labels)"""
     if inp[1] != inp[2] or out[1] != out[2]:
         raise ValueError(f"the y/x swap of SimpleAugment (transpose_only=[1, 2]) needs square blocks, not input {list(inp)} / output {list(out)}; "
-                         "set augment.simple = false")
+                         f"set {key}.simple = false")
 
 
 def draw_plan(rng, params, shape, voxel_size):

@@ -27,8 +27,8 @@ Declared quirks of the reference, both kept or named:
   * DefectAugment's axis=1 counts one axis and cuts another: gp/defect_augment.py:142 draws one r per index of the SPATIAL
     ROI's axis 1, which is H, and :199-202 applies index i to the 4-D data's axis 1, which is z; indices >= D select nothing.
     Here D values are drawn, one per section; the reference's surplus H - D draws act on nothing.
-NOT built: DefectAugment's missing, deformed and artifact sections (0 / absent in the reference's call); SimpleAugment,
-DeformAugment and ShiftAugment of the synthetic labels.
+NOT built: DefectAugment's missing, deformed and artifact sections (0 / absent in the reference's call).  SimpleAugment,
+DeformAugment and ShiftAugment of the synthetic labels have a key of their own, `label_augment` (augment_labels.py, section 7o).
 """
 import ctypes as C
 import dataclasses

@@ -22,7 +22,9 @@ intensity nodes of raw after it, one launch per node for the ten draws (csrc/aug
 `SyntheticSource` feeds the second-stage setups (models/3d_affs_from_*/train.py) from labels made on the device (synth_labels.py, csrc/synth.hip), with
 `synthetic_labels = true` in the train config; with `input_augment` beside it every input array runs through the reference's degradation of
 the inputs (noise, intensity per channel and per section, smoothing per section, low contrast: augment_inputs.py, csrc/augment_inputs.hip;
-specified rules, section 7n).  The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
+specified rules, section 7n), and with `label_augment` the labels themselves run through SimpleAugment -> DeformAugment -> ShiftAugment
+directly after they are created, zeros entering from outside the block (augment_labels.py, the launches of csrc/augment.hip; section 7o).
+The arithmetic of the step itself is libbsmi (csrc/train*.hip; the targets: csrc/train_targets.hip).
 """
 import ctypes as C
 import glob
@@ -613,15 +615,26 @@ class SyntheticSource:
     net_config["inputs"] order: the random.Random(seed) stream is not touched, so gt_affs and affs_weights are those of the
     un-augmented source batch by batch, and so is raw where no node of a plan is applied.  None (the default): today's batches.
 
-    NOT built (logged by run_training): SimpleAugment, DeformAugment, ShiftAugment of the labels; without `input_augment` also
-    the Noise / Intensity / Smooth / Defect augmentations of the inputs."""
+    label_augment: an augment_labels.LabelAugParams (or True for the reference's arguments) turns on SimpleAugment -> DeformAugment
+    -> ShiftAugment of the labels, where the reference has them: directly behind CreateLabels, before CustomGrowBoundary and
+    ObfuscateLabels, so the inputs and the targets are all made from the warped labels.  One coordinate map of the block and one
+    nearest resampling (augment_labels.warp_labels: the launches of csrc/augment.hip; labels are 0 outside the block, DESIGN.md
+    section 7o).  Its plans (augment.draw_plan's order) come from a stream of their own, np.random.default_rng((seed, 2)): the
+    random.Random(seed) stream and the (seed, 1) stream are not touched.  None (the default): today's batches, bit for bit, with
+    or without `input_augment`.
+
+    NOT built (logged by run_training): without `label_augment` SimpleAugment, DeformAugment, ShiftAugment of the labels; without
+    `input_augment` the Noise / Intensity / Smooth / Defect augmentations of the inputs; with both DefectAugment's missing, deformed
+    and artifact sections, which are 0 or absent in the reference's call."""
 
     NOT_BUILT = ("SimpleAugment, DeformAugment and ShiftAugment of the labels; NoiseAugment, IntensityAugment, SmoothAugment and "
                  "DefectAugment of the inputs")
     NOT_BUILT_WITH_INPUT_AUGMENT = ("SimpleAugment, DeformAugment and ShiftAugment of the labels; DefectAugment's missing, deformed and "
                                     "artifact sections of the inputs (0 / absent in the reference's call)")
+    NOT_BUILT_WITH_LABEL_AUGMENT = "NoiseAugment, IntensityAugment, SmoothAugment and DefectAugment of the inputs"
+    NOT_BUILT_WITH_BOTH = "DefectAugment's missing, deformed and artifact sections of the inputs (0 / absent in the reference's call)"
 
-    def __init__(self, net_config, voxel_size=(1, 1, 1), device=0, seed=42, input_augment=None):
+    def __init__(self, net_config, voxel_size=(1, 1, 1), device=0, seed=42, input_augment=None, label_augment=None):
         from .synth_labels import anisotropy_range
         ins = net_config.get("inputs", {})
         keys = set(ins)
@@ -655,6 +668,15 @@ class SyntheticSource:
             input_augment = InputAugParams()
         self.input_augment = input_augment
         self.aug_rng = np.random.default_rng((int(seed), 1)) if input_augment is not None else None
+        self.label_augment, self.label_params, self.label_rng = None, None, None
+        if label_augment is not None and label_augment is not False:
+            from .augment_labels import LabelAugParams, check_block
+            self.label_augment = LabelAugParams() if label_augment is True else label_augment
+            # refusals before any GPU work: a swap of a non-square block, a rotation on an anisotropic section grid, a control
+            # lattice larger than the coordinate launch holds
+            check_block(self.label_augment, self.inp, self.vs)
+            self.label_params = self.label_augment.to_aug_params(self.vs)   # what augment.draw_plan takes
+            self.label_rng = np.random.default_rng((int(seed), 2))
 
     def __iter__(self):
         return self
@@ -666,10 +688,15 @@ class SyntheticSource:
         return self.engine
 
     def labels(self):
-        """(clean labels after the inputs' grow_boundary, obfuscated labels): int64 CUDA of input_shape"""
+        """(clean labels after the inputs' grow_boundary, obfuscated labels): int64 CUDA of input_shape.  The order is the
+        reference's: create_labels -> the warp of `label_augment`, where set -> grow_boundary -> obfuscate."""
         from .synth_labels import draw_plan
         eng = self._engine()
         lab = eng.create_labels(draw_plan(self.rng, self.inp, self.aniso))
+        if self.label_augment is not None:
+            from . import augment
+            from .augment_labels import warp_labels
+            lab = warp_labels(lab, augment.draw_plan(self.label_rng, self.label_params, self.inp, self.vs))
         if self.in_grow > 0:
             lab = eng.grow_boundary(lab, self.rng.getrandbits(64), self.in_grow)
         return lab, eng.obfuscate(lab, self.rng)
@@ -819,12 +846,20 @@ def make_sample_source(config, net_config, device=0, rank=0):
                                   " (its raw has the keys `augment` and `augment2d` with `intensity` inside)") + "; it degrades the inputs "
                                   "of the second-stage setups (3d_affs_from_2d_lsd, _2d_affs, _2d_mtlsd, _3d_lsd) and goes together with "
                                   "`synthetic_labels = true`")
+    from .augment_labels import LabelAugParams
+    label_augment = LabelAugParams.from_config(config.get("label_augment"))
+    if label_augment is not None and not (second_stage and config.get("synthetic_labels", False)):
+        raise NotImplementedError(f"label_augment: not built for the {setup_name(net_config)} setup" + ("" if second_stage else
+                                  " (its samples have the keys `augment` and `augment2d`)") + "; it warps the synthetic labels "
+                                  "of the second-stage setups (3d_affs_from_2d_lsd, _2d_affs, _2d_mtlsd, _3d_lsd) and goes together with "
+                                  "`synthetic_labels = true`")
     if second_stage:
         if not config.get("synthetic_labels", False):
             raise NotImplementedError(f"the {setup_name(net_config)} setup trains on synthetic labels (CreateLabels / ObfuscateLabels), which "
                                       "the built-in sample source makes only when the train config sets `synthetic_labels = true`; "
                                       "without it it feeds 2d_affs, 2d_lsd, 2d_mtlsd, 3d_affs, 3d_lsd and 3d_mtlsd")
-        return SyntheticSource(net_config, config.get("voxel_size", (1, 1, 1)), device=device, seed=42 + int(rank), input_augment=input_augment)
+        return SyntheticSource(net_config, config.get("voxel_size", (1, 1, 1)), device=device, seed=42 + int(rank), input_augment=input_augment,
+                               label_augment=label_augment)
     if outs and not set(outs) - {"2d_affs", "2d_lsds"}:
         s = training_settings(net_config)
         return SectionSource(config["samples"], net_config["input_shape"], net_config["output_shape"], int(net_config.get("adj_slices", 1)),
@@ -939,7 +974,15 @@ def run_training(config_file, device=0, batches=None, log=print):
             log("note: the reference's gunpowder augmentations are not part of this engine; samples are random crops "
                 "(`augment = true` turns on the geometric chain of the 3-D setups, `augment2d = true` that of the 2-D setups)")
         batches = make_sample_source(config, net_config, device, rank)
-        if isinstance(batches, SyntheticSource) and batches.input_augment is not None:
+        if isinstance(batches, SyntheticSource) and batches.label_augment is not None:
+            from .augment_inputs import NODES
+            if batches.input_augment is not None:
+                log("note: synthetic labels (synthetic_labels = true) with the geometric augmentation of the labels (`label_augment`) and "
+                    f"the input augmentation ({NODES}: `input_augment`) on the device; not built: {SyntheticSource.NOT_BUILT_WITH_BOTH}")
+            else:
+                log("note: synthetic labels (synthetic_labels = true) with the geometric augmentation of the labels on the device "
+                    f"(`label_augment`); not built: {SyntheticSource.NOT_BUILT_WITH_LABEL_AUGMENT} (`input_augment = true` turns them on)")
+        elif isinstance(batches, SyntheticSource) and batches.input_augment is not None:
             from .augment_inputs import NODES
             log(f"note: synthetic labels (synthetic_labels = true) with the input augmentation on the device ({NODES}: `input_augment`); "
                 f"not built: {SyntheticSource.NOT_BUILT_WITH_INPUT_AUGMENT}")

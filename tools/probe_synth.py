@@ -10,7 +10,11 @@ train    steps/s of a training run of the same setup fed by that source through 
 augin    the input augmentation (`input_augment`): device-event ms per launch and per array (every node
          applied) at the two shipped input arrays, (6, 24, 148, 148) and (10, 24, 148, 148); then batches/s of the source and
          steps/s of the fed trainer without the key, with it, and without it again, in this one session.
-`--only stages|source|train|augin`; `--batches N` (default 20)."""
+labelaug the geometric augmentation of the labels (`label_augment`) at the shipped block (24, 148, 148):
+         device-event ms of the pad, the coordinate launch and the resampling launch, and of warp_labels as a whole (with the plan's
+         uploads); then batches/s of the source and steps/s of the fed trainer without the key, with it, and without it again, in
+         this one session.
+`--only stages|source|train|augin|labelaug`; `--batches N` (default 20)."""
 import argparse, json, os, random, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -95,8 +99,8 @@ def stages_part():
     return {"part": "stages", "generated_shape": list(gen), "labels_in_volume": len(ids), "ms": res}
 
 
-def source_part(batches, input_augment=None):
-    src = SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment)
+def source_part(batches, input_augment=None, label_augment=None):
+    src = SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment, label_augment=label_augment)
     next(src)
     torch.cuda.synchronize()
     per = []
@@ -105,7 +109,7 @@ def source_part(batches, input_augment=None):
         next(src)
         torch.cuda.synchronize()
         per.append(time.perf_counter() - t)
-    return {"part": "source", "input_augment": input_augment is not None, "batches": batches, "batches_per_s": batches / sum(per), "ms_median": 1e3 * float(np.median(per)),
+    return {"part": "source", "input_augment": input_augment is not None, "label_augment": label_augment is not None, "batches": batches, "batches_per_s": batches / sum(per), "ms_median": 1e3 * float(np.median(per)),
             "ms_min": 1e3 * min(per), "ms_max": 1e3 * max(per)}
 
 
@@ -118,9 +122,9 @@ def make_trainer():
     return Trainer(model, settings["in_shape"], lr=settings["lr"])
 
 
-def fed(trainer, batches, input_augment=None):
+def fed(trainer, batches, input_augment=None, label_augment=None):
     """steps/s of `trainer` fed by the source through the prefetch thread, wall clock, and how long it waited for batches"""
-    src = PrefetchSource(SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment), 4, 0)
+    src = PrefetchSource(SyntheticSource(NET, VOXEL, 0, seed=42, input_augment=input_augment, label_augment=label_augment), 4, 0)
     try:
         for _ in range(3):
             trainer.training_step(next(src))
@@ -135,7 +139,7 @@ def fed(trainer, batches, input_augment=None):
         wall = time.perf_counter() - t
     finally:
         src.close()
-    return {"input_augment": input_augment is not None, "fed_steps_per_s": batches / wall, "waited_for_batches_s": waited, "wall_s": wall}
+    return {"input_augment": input_augment is not None, "label_augment": label_augment is not None, "fed_steps_per_s": batches / wall, "waited_for_batches_s": waited, "wall_s": wall}
 
 
 def augin_part(batches):
@@ -171,6 +175,29 @@ def augin_part(batches):
     return res
 
 
+def labelaug_part(batches):
+    from bootstrapper_amd import augment as G
+    from bootstrapper_amd import augment_labels as A
+    params = A.LabelAugParams()
+    on = A.LabelAugParams(shift_p=1.0)     # every node applied
+    plan = G.draw_plan(np.random.default_rng(1), on.to_aug_params(VOXEL), SHAPE, VOXEL)
+    lab = torch.randint(1, 2 ** 40, SHAPE, dtype=torch.int64, device="cuda")
+    pad = lambda: torch.nn.functional.pad(lab, (1, 1, 1, 1, 1, 1)).contiguous()  # noqa: E731
+    padded, coords = pad(), G.coords(plan, (-1, -1, -1), 0)
+    res = {"part": "labelaug", "voxels": int(lab.numel()), "lattice_nodes": int(np.prod(plan.lattice.shape[1:])),
+           "outside_share": float((A.warp_labels(lab, plan) == 0).float().mean()),
+           "ms": {"pad": events(pad), "coords_with_uploads": events(lambda: G.coords(plan, (-1, -1, -1), 0)),
+                  "sample_labels": events(lambda: G.sample_labels(coords, padded)), "warp_labels": events(lambda: A.warp_labels(lab, plan))},
+           "source": [], "train": []}
+    for key in (None, params, None):     # plain and augmented runs alternating in one session
+        res["source"].append({k: v for k, v in source_part(batches, label_augment=key).items() if k != "part"})
+    trainer = make_trainer()
+    for key in (None, params, None):
+        res["train"].append(fed(trainer, batches, label_augment=key))
+    trainer.close()
+    return res
+
+
 def train_part(batches):
     trainer = make_trainer()
     res = {"part": "train", "steps": batches}
@@ -193,11 +220,11 @@ def train_part(batches):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["stages", "source", "train", "augin"])
+    ap.add_argument("--only", choices=["stages", "source", "train", "augin", "labelaug"])
     ap.add_argument("--batches", type=int, default=20)
     a = ap.parse_args()
     for name, fn in (("stages", stages_part), ("source", lambda: source_part(a.batches)), ("train", lambda: train_part(a.batches)),
-                     ("augin", lambda: augin_part(a.batches))):
+                     ("augin", lambda: augin_part(a.batches)), ("labelaug", lambda: labelaug_part(a.batches))):
         if a.only in (None, name):
             print(json.dumps(fn()), flush=True)
 

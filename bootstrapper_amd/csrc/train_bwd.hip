@@ -111,6 +111,9 @@ __global__ void loss_grad_kernel(const float* __restrict__ p, const float* __res
 
 // head backward: p = sigmoid((Wc + Wr) z + bc + br).  dlogit = dp p (1 - p); dz (channels-last) += (Wc + Wr)^T dlogit;
 // dWc, dWr += dlogit z^T; dbc, dbr += dlogit.  One thread per voxel, block-level reduction of the weight gradients.
+// WIDE: more than 32 input channels (up to the 64 of the forward's head kernel): the voxel's channels are read where they are
+// used instead of being kept in a private array; the sums and their order are the same.
+template <bool WIDE>
 __global__ void head_bwd_kernel(const float* __restrict__ z, int zc, const float* __restrict__ p, const float* __restrict__ dp, size_t nvox,
                                 int cin, int cout, const float* __restrict__ hw, float* __restrict__ dz, float* __restrict__ gwc,
                                 float* __restrict__ gwr, float* __restrict__ gbc, float* __restrict__ gbr, float* __restrict__ part) {
@@ -151,8 +154,9 @@ __global__ void head_bwd_kernel(const float* __restrict__ z, int zc, const float
     return;
   }
   if (v < nvox) {
-    float zz[32], dl[16];
-    for (int c = 0; c < cin; ++c) zz[c] = z[v * zc + c];
+    float zz[WIDE ? 1 : 32], dl[16];
+    if constexpr (!WIDE)
+      for (int c = 0; c < cin; ++c) zz[c] = z[v * zc + c];
     for (int o = 0; o < cout; ++o) {
       const float pp = p[(size_t)o * nvox + v];
       dl[o] = dp[(size_t)o * nvox + v] * pp * (1.f - pp);
@@ -163,7 +167,7 @@ __global__ void head_bwd_kernel(const float* __restrict__ z, int zc, const float
       dz[v * zc + c] += acc;
     }
     for (int o = 0; o < cout; ++o) {
-      for (int c = 0; c < cin; ++c) atomicAdd(&red[o * cin + c], dl[o] * zz[c]);
+      for (int c = 0; c < cin; ++c) atomicAdd(&red[o * cin + c], dl[o] * (WIDE ? z[v * zc + c] : zz[c]));
       atomicAdd(&red[cout * cin + o], dl[o]);
     }
   }
@@ -484,13 +488,13 @@ int launch_head_bwd(bsmi_unet* h, const PlanStep& st, bool det, hipStream_t s) {
   const StageParams& par = ts->head_par[st.head];
   TDesc dz = ts->grad_of[st.in.ptr];
   float *gwc = ts->g + par.w->off, *gwr = ts->g + par.rw->off, *gbc = ts->g + par.b->off, *gbr = ts->g + par.rb->off;
-  if (hd.cin > 32 || hd.cout > 16) BSMI_FAIL(BSMI_ERR_INVALID, "head backward: at most 32 input and 16 output channels");
+  if (hd.cin > 64 || hd.cout > 16) BSMI_FAIL(BSMI_ERR_INVALID, "head backward: at most 64 input and 16 output channels");
   const size_t nv = ts->out_vox;
   const int nred = hd.cout * hd.cin + hd.cout;
   const unsigned hblocks = (unsigned)((nv + 255) / 256);
   int rc;
   if (det && (rc = grow_buf(s, &ts->det_part, &ts->det_part_bytes, (size_t)hblocks * nred * sizeof(float), false))) return rc;
-  hipLaunchKernelGGL(head_bwd_kernel, dim3(hblocks), dim3(256), (size_t)(det ? 4 : 1) * nred * sizeof(float), s,
+  hipLaunchKernelGGL(hd.cin > 32 ? head_bwd_kernel<true> : head_bwd_kernel<false>, dim3(hblocks), dim3(256), (size_t)(det ? 4 : 1) * nred * sizeof(float), s,
                      (const float*)st.in.ptr, st.in.Cpad, (const float*)ts->head_out[st.head], (const float*)ts->head_dp[st.head], nv, hd.cin,
                      hd.cout, (const float*)hd.hw, (float*)dz.ptr, gwc, gwr, gbc, gbr, det ? (float*)ts->det_part : (float*)nullptr);
   if (det) {  // the workgroups' rows in index order: weights, then biases

@@ -210,6 +210,10 @@ int bsmi_unet_finalize(bsmi_unet* h, int precision) {
   for (auto& kv : h->weights)
     if (!kv.second.loaded) missing += (missing.empty() ? "\"" : ", \"") + kv.first + "\"";
   if (!missing.empty()) BSMI_FAIL(BSMI_ERR_MISSING, "Missing key(s) in state_dict: %s", missing.c_str());
+  // launch_head's limit, refused here: a wider net would otherwise run its whole trunk and fail at the last launch of a forward
+  for (auto& hd : h->heads)
+    if (round_up(hd.cin, kChanPad) > 64)
+      BSMI_FAIL(BSMI_ERR_INVALID, "head kernel supports at most 64 input channels (%s reads %d)", hd.prefix.c_str(), hd.cin);
   BSMI_HIP(hipSetDevice(h->device));
   auto repack = [&](PassSite& p) -> int {
     for (int c = 0; c < p.nconv; ++c) {

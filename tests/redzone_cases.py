@@ -200,6 +200,8 @@ NOT_USED = {
     "tests/test_guards_gpu.py": "the guard run of the engines' own buffers (network, training step, volume pipeline)",
     "tests/test_large_sections_gpu.py": "runs its own guard worker; full-size sections",
     "tests/test_layers_gpu.py": "the network engine's own buffers: tests/guard_worker.py",
+    "tests/test_layers_edges_gpu.py": "the network engine's own buffers: tests/guard_worker.py",
+    "tests/test_backward_edges_gpu.py": "the training engine's own buffers: tests/guard_worker.py",
     "tests/test_conv_below_up_gpu.py": "the network engine's own buffers; a child process per switch",
     "tests/test_fuse_up_narrow_gpu.py": "the network engine's own buffers; a child process per switch",
     "tests/test_pool_fuse_gpu.py": "the network engine's own buffers; a child process per switch",

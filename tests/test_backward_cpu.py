@@ -12,7 +12,10 @@
                                columns omitted or read at offset 0 instead of crop / 2, a second slot's cbase off by one tile,
                                the last real channel of the last row missing, the pool gradient at the LAST maximum, the upper
                                interpolation neighbour not clamped at the far edge, a non-zero border voxel, `lo` planes dropped
-                               from the split copy, N of the loss over all elements, Adam without bias correction
+                               from the split copy, N of the loss over all elements, Adam without bias correction; and on a
+                               synthetic 65 -> 65 weight-gradient stage (the tile edges of case E, tests/edge_nets.py): the second
+                               C-tile's one real channel missing, row 64 zeroed, that channel leaking into column 63, one product
+                               off by one bf16 ulp
 
 Wall time: about 4 min on 8 threads (the float64 step of case C is computed once and shared).
 
@@ -240,6 +243,59 @@ def test_second_slot_cbase_off_by_one_tile_is_refused():
         dW = dW[:, :ct]
         oks = [B.check_wgrad(dW[:, p[3]:p[3] + p[5]], p[0], p[1], p[2], info, rng)[0] for p, info in zip(parts, infos)]
         assert all(oks) == (shift == 0), (shift, oks)
+
+
+# ---- a weight-gradient stage on the tile edges (tests/edge_nets.py, tests/test_backward_edges_gpu.py) -------------------------------
+_EDGE_WGRAD = {}
+
+
+def edge_wgrad_stage():
+    """65 -> 65 channels, 3x3x3, output (3, 10, 11): N = 65 is one row over the 64-row tile (the 128-row tile runs), C = 65 puts one
+    real channel into a second 64-channel C-tile.  g: a masked gradient (half of it exact zeros), x: post-ReLU activations.  Made once."""
+    if not _EDGE_WGRAD:
+        rng = np.random.default_rng(65)
+        g = (rng.standard_normal((3, 10, 11, 65)) * (rng.random((3, 10, 11, 65)) > 0.5)).astype(np.float32)
+        x = np.maximum(rng.standard_normal((5, 12, 13, 65)), 0).astype(np.float32)
+        _EDGE_WGRAD.update(g=g, x=x)
+    return _EDGE_WGRAD["g"], _EDGE_WGRAD["x"]
+
+
+@pytest.mark.parametrize("arith", ["f32", "split-bf16", "split-bf16+det"])
+def test_weight_gradient_stage_with_65_channels(arith):
+    """The emulations of the launch pass; refused are: the one real channel of the second C-tile never written, or written from the
+    padding channel beside it (zeros); row 64 -- the first of the tile's second half of 64 -- zeroed; the last real column of the
+    first C-tile (c = 63) with one product of every sum off by one bf16 ulp of its operand (f32 and split-bf16 both hold more
+    than bf16's 8 bits); the second C-tile's channel also added into c = 63 (a padding column leaking into its neighbour)."""
+    g, x = edge_wgrad_stage()
+    kernel, N, C = (3, 3, 3), 65, 65
+    Do, Ho, Wo, _ = g.shape
+    info = B.wgrad_plan(arith.split("+")[0], N, C, Do * Ho, 9, det=arith.endswith("+det"))
+    assert info["tile"] == ((128, 64) if arith.startswith("split") else (128, 128)), info
+    check = lambda dw: B.check_wgrad(dw, g, x, kernel, info, np.random.default_rng(5))
+    good = B.emulate_wgrad(g, x, kernel, info).astype(np.float32)
+    ok, worst, g_acc, e_fmt, e_acc = check(good)
+    print(f"65 x 65 {arith}: {info}  e_fmt {e_fmt:.2e} e_acc32 {e_acc:.2e} worst err/S {worst['max_err_over_S']:.2e}")
+    assert ok, worst
+    for order in ("ascending", "descending", "shuffled"):
+        assert check(B.emulate_wgrad_f32_accumulation(g, x, kernel, info, order))[0], order
+    bad = good.copy()
+    bad[:, 64, :] = 0
+    assert not check(bad)[0], "the second C-tile's real channel never written"
+    bad = good.copy()
+    bad[64, :, :] = 0
+    assert not check(bad)[0], "row 64 zeroed"
+    bad = good.copy()
+    bad[:, 63, :] += good[:, 64, :]
+    assert not check(bad)[0], "the second C-tile's channel added into the last column of the first"
+    # one product per sum: the voxel with the largest |x| of channel 63 under the centre tap, its x off by one bf16 ulp
+    xc = x[1:1 + Do, 1:1 + Ho, 1:1 + Wo, 63]
+    v = np.unravel_index(int(np.argmax(np.abs(xc) * np.abs(g).max(axis=3))), xc.shape)
+    ulp = 2.0 ** (np.floor(np.log2(abs(float(xc[v])))) - 7)
+    bad = good.copy()
+    bad[:, 63, 13] += (g[v].astype(np.float64) * ulp).astype(np.float32)
+    ok, worst = check(bad)[:2]
+    print(f"65 x 65 {arith}: one bf16 ulp of one product: err/S {worst['max_err_over_S']:.2e} against g_acc {g_acc:.2e}")
+    assert not ok, "one product of column 63 off by one bf16 ulp"
 
 
 # ---- input gradients ---------------------------------------------------------------------------------------------------------------

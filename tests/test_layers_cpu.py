@@ -1,6 +1,7 @@
 """The per-launch comparison of tests/layer_ref.py has to detect: on synthetic stages, with emulations of the kernels'
 arithmetic standing in for the kernels, every emulation passes the gate that tests/test_layers_gpu.py holds the MI355X
-to, and every injected fault fails it.  No GPU.
+to, and every injected fault fails it.  No GPU.  The stages e64 / e65 / e161 / e305 stand at the channel counts of case E
+(tests/edge_nets.py) with the faults of a tile or padding edge: EDGE_FAULT_CASES.
 
 Gates as in layer_ref: |got - ref| <= g_acc S + g_out |ref| with g_acc = 4 max(e_fmt, e_acc32), both from the reference.
 """
@@ -46,7 +47,11 @@ def make_stage(name, prec, seed=0):
         res = [(skip, tuple(o + 1 for o in so), 24), (up, (1, 1, 1), 40)]
         return L.Stage(src, k, w, b, res, wr, br), (3, 14, 12, 24)
     cin, cout, k, shape = {"c12": (12, 12, (3, 3, 3), (6, 14, 15)), "c60": (60, 60, (3, 3, 3), (5, 16, 15)),
-                           "c300": (300, 64, (3, 3, 3), (5, 16, 15)), "k133": (60, 60, (1, 3, 3), (3, 16, 15))}[name]
+                           "c300": (300, 64, (3, 3, 3), (5, 16, 15)), "k133": (60, 60, (1, 3, 3), (3, 16, 15)),
+                           # the channel counts of tests/edge_nets.py: an exact fit of the 64-column tile, one over it, one over 160
+                           # (eleven 16-channel units), and 304 of 320 columns read from twenty units, the last with one channel
+                           "e64": (64, 64, (3, 3, 3), (5, 12, 13)), "e65": (65, 65, (3, 3, 3), (5, 12, 13)),
+                           "e161": (161, 161, (3, 3, 3), (5, 12, 13)), "e305": (305, 304, (3, 3, 3), (5, 12, 13))}[name]
     x = L.Dense(_acts(rng, shape + (cin,), prec))
     w, b = _weights(rng, cout, cin, k)
     return L.Stage([(x, (0, 0, 0), cin)], k, w, b), tuple(shape[d] - k[d] + 1 for d in range(3)) + (cout,)
@@ -142,6 +147,116 @@ def test_omitted_bias_is_inside_the_bf16_format():
     ok, worst = _check(st, st.emulate(X, "bf16", fault=("bias", 3)), pre, S, g_acc, "bf16")
     print(f"omitted bias in bf16: err/S {worst['max_err_over_S']:.3e}, g_acc {g_acc:.3e}, format {e_fmt:.3e}")
     assert ok and e_fmt < worst["max_err_over_S"] < g_acc
+
+
+# ---- the channel counts on the tile and padding edges (tests/edge_nets.py, tests/test_layers_edges_gpu.py) ------------------------
+EDGE_STAGES = ["e64", "e65", "e161", "e305"]
+# the column at which a second N-tile (or a second column half of a wide tile) of the stage begins
+SECOND_TILE = {"e65": 64, "e161": 160, "e305": 256}
+# exact_ulp     the last real column of a tile that the stage fills exactly has one product wrong by one bf16 ulp of its weight
+# tile2_zero    the first column of a second N-tile zeroed
+# unit_channel  one channel of the last 16-channel unit (the only real one where cin = 16 n + 1) left out of the sum, every tap
+# pad_leak      a padding column's (zero) weights of one tap land in column cout - 1: that tap is missing there
+# exact_ulp is asserted in f32 and in the split mode: one bf16 ulp of one product is what the bf16 mode's own weights carry on
+# every product (pinned by test_one_bf16_ulp_of_one_product_is_inside_the_bf16_format)
+EDGE_FAULT_CASES = ([("e64", "exact_ulp", p) for p in ("f32", "bf16x3")] +
+                    [(n, "tile2_zero", p) for n in SECOND_TILE for p in PRECS] +
+                    [(n, "unit_channel", p) for n in ("e65", "e161", "e305") for p in PRECS] +
+                    [(n, "pad_leak", p) for n in ("e65", "e161", "e305") for p in PRECS])
+_EDGE_SETUP = {}
+
+
+def _edge_setup(name, prec):
+    """_setup of an edge stage, computed once per (stage, precision) and shared; nothing changes it"""
+    if (name, prec) not in _EDGE_SETUP:
+        _EDGE_SETUP[name, prec] = _setup(name, prec)
+    return _EDGE_SETUP[name, prec]
+
+
+def _edge_fault(st, X, prec, fault, name):
+    """the emulation's sums with one fault of EDGE_FAULT_CASES"""
+    c = st.cols
+    last = st.cout - 1
+    if fault == "exact_ulp":
+        bad = st.emulate(X, prec)
+        k = int(np.argmax(np.abs(st.W32[:, last])))                     # the column's largest weight: one K index
+        ulp = 2.0 ** (np.floor(np.log2(abs(float(st.W32[k, last])))) - 7)   # spacing of bf16 at that weight
+        bad[:, last] += X[:, k] * ulp
+        return bad
+    if fault == "tile2_zero":
+        bad = st.emulate(X, prec)
+        bad[:, SECOND_TILE[name]] = 0.0
+        return bad
+    if fault == "unit_channel":
+        cin = int(c[:, 3].max()) + 1
+        assert (cin - 1) // L.CHAN_PAD == -(-cin // L.CHAN_PAD) - 1 and (cin - 1) % L.CHAN_PAD == 0   # alone in the last unit
+        Xb = X.copy()
+        Xb[:, c[:, 3] == cin - 1] = 0.0
+        return st.emulate(Xb, prec)
+    assert fault == "pad_leak"
+    full = st.emulate(X, prec)
+    Xb = X.copy()
+    Xb[:, c[:, 2] == len(st.taps) // 2] = 0.0                             # the centre tap's rows of K
+    full[:, last] = st.emulate(Xb, prec)[:, last]
+    return full
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("name", EDGE_STAGES)
+def test_edge_stage_emulation_passes_its_own_gate(name, prec):
+    st, shape, vox, X, pre, S, g_acc, e_fmt, e_acc = _edge_setup(name, prec)
+    print(f"{name} {prec}: K = {X.shape[1]}  e_fmt {e_fmt:.3e}  e_acc32 {e_acc:.3e}  g_acc {g_acc:.3e}")
+    assert len(X) > L.M_TILE and len(X) % L.M_TILE
+    ok, worst = _check(st, st.emulate(X, prec), pre, S, g_acc, prec)
+    assert ok, L.describe(worst, vox, shape)
+    if prec == "f32":
+        ok, worst = _check(st, st.acc32_torch(X), pre, S, g_acc, prec)
+        assert ok, L.describe(worst, vox, shape)
+        acc, pre_s, S_s = st.acc32_sequential(X, prec, max_rows=1 << 30, max_cols=1 << 30)
+        ok, worst = _check(st, acc, pre, S, g_acc, prec)
+        assert ok, L.describe(worst, vox, shape)
+
+
+@pytest.mark.parametrize("name,fault,prec", EDGE_FAULT_CASES)
+def test_edge_fault_fails_the_gate(name, fault, prec):
+    st, shape, vox, X, pre, S, g_acc, e_fmt, e_acc = _edge_setup(name, prec)
+    ok, worst = _check(st, _edge_fault(st, X, prec, fault, name), pre, S, g_acc, prec)
+    print(f"{name} {prec} {fault}: worst err/S {worst['max_err_over_S']:.3e} against g_acc {g_acc:.3e} (format {e_fmt:.3e}), "
+          f"{L.describe(worst, vox, shape)}")
+    assert not ok, f"{fault} passes the gate of {name} in {prec}: largest err/S {worst['max_err_over_S']:.3e}, g_acc {g_acc:.3e}"
+    if fault in ("exact_ulp", "pad_leak"):
+        assert worst["channel"] == st.cout - 1, worst           # and the message points at the column
+    if fault == "tile2_zero":
+        assert worst["channel"] == SECOND_TILE[name], worst
+
+
+def test_one_bf16_ulp_of_one_product_is_inside_the_bf16_format():
+    """The pair this comparison cannot separate at the exact-fit stage: in the bf16 mode every weight is rounded to bf16, half an
+    ulp at the worst on each of the K = 1 728 products; one product of the last column off by a whole ulp is of that size, and
+    stays under the gate that the format's own error sets.  f32 and the split mode refuse it (EDGE_FAULT_CASES)."""
+    st, shape, vox, X, pre, S, g_acc, e_fmt, e_acc = _edge_setup("e64", "bf16")
+    ok, worst = _check(st, _edge_fault(st, X, "bf16", "exact_ulp", "e64"), pre, S, g_acc, "bf16")
+    print(f"one ulp of one product in bf16: err/S {worst['max_err_over_S']:.3e}, g_acc {g_acc:.3e}, format {e_fmt:.3e}")
+    assert ok and worst["max_err_over_S"] < g_acc
+
+
+def test_edge_net_shapes_keep_their_properties():
+    """What the input shapes of tests/edge_nets.py were chosen for: every stage of E1 - E12 has more than one 256-row tile and a
+    partial last one; the level-1 and decoder stages have overhanging and exact 4 x 4 tiles in y and in x; the counts of the table."""
+    import edge_nets as E
+    for tag in E.TAGS:
+        convs = [o for o in L.walk(E.net_config(tag), E.shape_of(tag)) if o["type"] == "conv"]
+        rows = [o["shape"][0] * o["shape"][1] * o["shape"][2] for o in convs]
+        if tag != "E13":
+            assert rows == E.STAGE_ROWS, (tag, rows)
+            assert all(r > L.M_TILE and r % L.M_TILE for r in rows)
+            ys, xs = {o["shape"][1] for o in convs[2:]}, {o["shape"][2] for o in convs[2:]}
+            assert {v % 4 for v in ys} == {0, 2} and {v % 4 for v in xs} == {0, 2}, (ys, xs)
+        else:
+            assert (rows[5], rows[7], rows[9]) == (270, 240, 96), rows
+        assert convs[-1]["shape"][3] <= 64      # the head's limit
+    deepest = {tag: max(o["shape"][3] for o in L.walk(E.net_config(tag), E.shape_of(tag)) if o["type"] == "conv") for tag in E.TAGS}
+    assert list(deepest.values()) == [64, 33, 65, 160, 161, 256, 304, 305, 320, 400, 480, 528, 640], deepest
 
 
 @pytest.mark.parametrize("m", [2, 4])
